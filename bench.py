@@ -14,11 +14,15 @@ outputs (reference shape: scripts/train_seq2seq.py:125-138, H = 500 there).  One
 8 patients x 2048 trials sharded over 8 GPUs -- with dropout 0.3 / 0.3, teacher forcing 0.5, clip 0.5, AdamW as in the
 reference script (:171-189).  Weak scaling: every rank holds its own 2048-trial shard; BatchNorm statistics and the flat
 gradient are all-reduced.  `--workload configs1` measures BASELINE.json configs[1] (single patient, C = 64, H = 128) instead;
-the default run carries it as a sub-record.
+a `--full` run carries it as a sub-record.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel of the step, HIP-event timed) and `cpu_baseline` (the CPU
-oracle = torch.nn restatement of the reference on the SAME full batch, bounded sample) plus sub-records (single process
-only): `configs1`, `fp32`, `alignment` (8 views), `realtime` (config 5) and `dp_rehearsal`.
+Prints ONE JSON line (rank 0): the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  A plain
+run does only that: set-up, pre-warm + W warm-up steps, K timed steps, the line.  `--full` adds (single process only)
+`roofline` (dominant kernel of the step, HIP-event timed), `cpu_baseline` (the CPU oracle = torch.nn restatement of the
+reference on the SAME full batch, bounded sample) and the sub-records `configs1`, `fp32`, `alignment` (8 views), `realtime`
+(config 5) and `dp_rehearsal`; `--headline-only`, `--no-probes` and `--no-cpu-baseline` leave parts of it out again.
+`--dump-outputs DIR` writes what the last timed step computed (loss, logits, the updated parameters and BatchNorm statistics)
+as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -395,6 +399,7 @@ def _make_step(c, dev, rank, dropout=0.3, group=None, world=1):
     X, y = X.to(dev), y.to(dev)                  # inputs resident in HBM before any timed region
     model.train()
     one = XF.unit_gradient(dev)
+    last = {}
 
     def step():
         opt.zero_grad()
@@ -402,8 +407,31 @@ def _make_step(c, dev, rank, dropout=0.3, group=None, world=1):
         loss = model.criterion(logits.view(-1, c['num_classes']), y.view(-1))
         loss.backward(one)                       # a resident 1.0 as the root gradient (autograd would launch a fill)
         opt.step()
+        last['logits'] = logits.detach()         # (detached: keeps no graph of the step alive)
         return loss
+    step.last = last                             # the logits of the latest step (for --dump-outputs)
     return model, step
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, step, loss):
+    """What the last step handed its caller, as <name>.npy (float32): the loss, the logits and the state the optimiser
+    step left behind (every parameter and the BatchNorm running statistics, named by their state_dict keys)."""
+    import numpy as np
+    arrays = {'loss': loss.detach(), 'logits': step.last['logits']}
+    for k, v in model.state_dict().items():
+        if v.is_floating_point():
+            arrays[k] = v.detach()
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit')
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    return sorted(arrays)
 
 
 def workload_record(name, dev, steps, warm, with_roofline=True):
@@ -625,13 +653,17 @@ def main():
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--workload', choices=sorted(WORKLOADS), default='configs3')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--headline-only', action='store_true', help='skip the sub-records')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure beyond the headline (single process): roofline probes, sub-records, CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--headline-only', action='store_true', help='with --full: skip the sub-records')
     ap.add_argument('--no-probes', action='store_true',
-                    help='profiling runs only: skip the roofline probes too (their re-issued launches would be counted into a per-step '
-                         'kernel profile); the line then has no roofline')
+                    help='with --full, profiling runs only: skip the roofline probes too (their re-issued launches would be counted into a '
+                         'per-step kernel profile); the line then has no roofline')
     ap.add_argument('--precision', choices=['bf16x3', 'fp32'], default=None,
                     help='product precision of the matrix kernels (default: the library default, bf16x3)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (loss, logits, updated parameters) as DIR/<name>.npy, float32')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -693,6 +725,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
     final_loss = float(loss.item())
+    dumped = dump_outputs(args.dump_outputs, model, step, loss) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         trials = c['trials_per_gpu'] * world * args.steps
@@ -718,9 +751,12 @@ def main():
         out['config']['collective'] = (f'RCCL (torch.distributed backend {backend!r}) world {world}: SyncBN statistics + flat gradient '
                                        f'all-reduce per step' if world > 1 else 'none (single process)')
         out['rccl_world'] = world if (world > 1 and backend == 'nccl') else (0 if world == 1 else None)
-        if world == 1 and args.no_probes:
+        if dumped is not None:
+            out['outputs'] = {'dir': args.dump_outputs, 'arrays': len(dumped), 'dtype': 'float32'}
+        # a plain run stops here: the headline alone; what follows is --full
+        if args.full and world == 1 and args.no_probes:
             out['roofline'] = None
-        elif world == 1:
+        elif args.full and world == 1:
             # (single process only: the roofline probes re-issue launches, a capture runs one more training step)
             try:
                 out['roofline'] = (roofline_cluster(model, c, dev) if name == 'configs3'
@@ -741,7 +777,7 @@ def main():
                         out[key] = fn()
                     except Exception as e:                                   # noqa: BLE001
                         out[key] = {'error': f'{type(e).__name__}: {e}'[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 _set_affinity_all_threads(full_affinity)        # the CPU oracle gets every core of the host share
                 out['cpu_baseline'] = cpu_baseline(c)

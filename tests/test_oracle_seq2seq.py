@@ -10,12 +10,22 @@ import torch
 from oracle.seq2seq_oracle import Seq2SeqOracle, cmat_acc, phoneme_error_rate, train_step
 from weights import weights_from_seed
 
+LR = 1e-3
+# Adam's first step moves a weight by lr * g / (|g| + eps), eps = 1e-8, so where |g| is near zero a last-bit difference of
+# the gradient moves the weight by a visible fraction of lr.  The gradients themselves agree across CPU kernels (AVX2 /
+# AVX-512 / other vendors' BLAS paths: <= 5e-9 measured), but the updated value of such an element does not: the conv bias
+# (it feeds a train-mode BatchNorm, so its gradient is analytically zero and numerically rounding noise) and single
+# elements of the weight matrices.  Elements whose reference gradient is >= ADAM_STABLE_GRAD are held to the full
+# tolerance; the others to the bound of the step itself (< lr on each side).
+ADAM_STABLE_GRAD = 1e-6
+NOISE_KEY = 'temporal_conv.conv.bias'
+
 
 def build(g):
     cfg = ast.literal_eval(str(g['cfg']))
     m = Seq2SeqOracle(cfg['in_channels'], cfg['n_filters'], cfg['hidden_size'], 9, cfg['n_enc_layers'],
                       cfg['n_dec_layers'], cfg['kernel_size'], cfg['stride'], 0, 0.0, 0.0,
-                      learning_rate=1e-3, l2_reg=1e-5, activation=cfg['activation'], decay_iters=5)
+                      learning_rate=LR, l2_reg=1e-5, activation=cfg['activation'], decay_iters=5)
     sd = weights_from_seed(m.state_dict(), int(g['seed']))
     m.load_state_dict(sd)
     return m, sd
@@ -51,12 +61,24 @@ def test_train_step_matches_reference(golden_dir, name, tag, coin):
         for k, p in grads.items():
             np.testing.assert_allclose(p.grad.numpy(), g[f'{tag}_grad/{k}'], rtol=1e-4, atol=1e-7)
         for k, v in m.state_dict().items():
-            np.testing.assert_allclose(v.numpy(), g[f'{tag}_after/{k}'], rtol=1e-5, atol=1e-7)
+            got, ref = v.numpy(), g[f'{tag}_after/{k}']
+            gr = np.abs(g[f'{tag}_grad/{k}']) if f'{tag}_grad/{k}' in g else np.full(ref.shape, np.inf)
+            stable = gr >= ADAM_STABLE_GRAD
+            np.testing.assert_allclose(got[stable], ref[stable], rtol=1e-5, atol=1e-7, err_msg=k)
+            assert np.all(np.abs(got[~stable] - ref[~stable]) <= 2 * LR), k
     else:
         for k, p in grads.items():
-            np.testing.assert_allclose(p.grad.norm().numpy(), g[f'{tag}_gradnorm/{k}'], rtol=1e-4)
-        after = np.array([v.double().sum().item() for v in m.state_dict().values()])
-        np.testing.assert_allclose(after, g[f'{tag}_after_sum'], rtol=1e-6, atol=1e-6)
+            # (atol: the conv bias's gradient norm is ~3e-9 of rounding noise; every other norm is orders above it)
+            np.testing.assert_allclose(p.grad.norm().numpy(), g[f'{tag}_gradnorm/{k}'], rtol=1e-4, atol=1e-7, err_msg=k)
+        sd_after = m.state_dict()
+        after = np.array([v.double().sum().item() for v in sd_after.values()])
+        ref = g[f'{tag}_after_sum']
+        # sums over up to 1e5 elements, a few hundred of them with near-zero gradients: lr / 5 is below one element's step
+        # gone the other way (up to 2 lr) and above what those elements add across CPU kernels (<= 5e-5 measured); the
+        # conv bias, every element of it at the noise floor, is held to the step bound
+        atol = np.array([2 * LR * v.numel() if k == NOISE_KEY else LR / 5 for k, v in sd_after.items()])
+        bad = np.abs(after - ref) > atol + 1e-6 * np.abs(ref)
+        assert not bad.any(), [(k, after[i], ref[i]) for i, k in enumerate(sd_after) if bad[i]]
 
 
 def test_state_dict_keys_are_the_reference_keys():

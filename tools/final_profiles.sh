@@ -2,7 +2,7 @@
 # End-of-round evidence in one GPU call: default bench line, rocprofv3 kernel stats (serial streams) of both workloads, step
 # timelines with the side stream.  Outputs under gpurun_out/final/.
 R=$PWD; O=$R/gpurun_out/final; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json; echo
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json; echo
 cd /tmp && export TMPDIR=/tmp
 prof() {  # name, env assignments, bench args
   local name=$1 envs=$2; shift 2
