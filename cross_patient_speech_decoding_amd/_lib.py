@@ -102,6 +102,8 @@ SIGNATURES = {
     'xps_scatter_rows_f32_workspace': (_sz, [_i, _i, _i]),
     'xps_scatter_rows_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     'xps_next_token': (_i, [_vp, _i, _vp, _i64, _vp, _vp, _i, _vp]),
+    'xps_window_shift_f32': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'xps_ctc_collapse_f32': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     'xps_decoder_select_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'xps_dropout_f32': (_i, [_vp, _vp, _vp, _i64, _f, C.c_uint64, _vp]),
     'xps_split4_f32': (_i, [_vp, _vp, _i64, _f, C.c_uint64, _vp]),
@@ -133,6 +135,8 @@ SIGNATURES = {
     'xps_apply_f64': (_i, [_vp, _i, _i64, _vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _vp]),
     'xps_process_hg_f64_workspace': (_sz, [_i, _i, _i]),
     'xps_process_hg_f64': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'xps_pipe_frontend_f64_workspace': (_sz, [_i, _i, _i, _i]),
+    'xps_pipe_frontend_f64': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'xps_aug_time_shift_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'xps_aug_time_mask_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'xps_aug_scale_f32': (_i, [_vp, _vp, _i64, _f, _vp]),

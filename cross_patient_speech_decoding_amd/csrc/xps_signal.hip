@@ -158,3 +158,124 @@ extern "C" int xps_process_hg_f64(const double* data, int C, int Tn, const uint8
     XPS_CHECK_LAUNCH();
     return XPS_OK;
 }
+
+// Multi-bin, multi-stream frontend of the realtime pipeline (realtime_sim/realtime_pipeline.py): k consecutive bins of
+// n_streams streams in one launch; bin j of stream s is exactly process_HG(bins[s][j], filt_ics=<state after bin j-1>).
+// Grid (C / HG_CPB, n_streams); a block walks the k bins in order and keeps its (channel, band) filter state in registers
+// across them, so each recurrence runs sequentially over k x Tn samples.  Per bin the arithmetic is process_hg_kernel's:
+// CAR summed in channel order, DF-II-transposed without fma, numpy's pairwise sum over the bin's own (Tn x bands) block.
+// The squared filter output is written directly (y * y is the value np.square produces from the stored y).
+// MAXT bounds the taps at compile time: the tap loops unroll with guards, so coefficients and state stay in registers.
+namespace {
+template <int MAXT>
+__global__ __launch_bounds__(256) void pipe_frontend_kernel(const double* __restrict__ bins, int k, int C, int Tn,
+                                     const unsigned char* __restrict__ good, const double* __restrict__ bcoef,
+                                     const double* __restrict__ acoef, int bands, int taps, double* __restrict__ zi,
+                                     double* __restrict__ sq, double* __restrict__ power) {
+#pragma clang fp contract(off)
+    __shared__ double avg[HG_MAXT];
+    const int tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y;
+    const int c0 = blockIdx.x * HG_CPB;
+    const unsigned char* gs = good ? good + (long long)s * C : nullptr;
+    int ngood = 0;
+    for (int c = 0; c < C; ++c) ngood += (!gs || gs[c]) ? 1 : 0;
+    const int cl = tid / bands, band = tid % bands;
+    const int c = c0 + cl;
+    const bool filt = cl < HG_CPB && c < C;
+    double b[MAXT], a[MAXT], z[MAXT];
+    double* zp = nullptr;
+#pragma unroll
+    for (int q = 0; q < MAXT; ++q) { b[q] = 0.0; a[q] = 0.0; z[q] = 0.0; }
+    if (filt) {
+        const double a0 = acoef ? acoef[(long long)band * taps] : 1.0;
+#pragma unroll
+        for (int q = 0; q < MAXT; ++q)
+            if (q < taps) {
+                b[q] = bcoef[(long long)band * taps + q] / a0;
+                a[q] = acoef ? acoef[(long long)band * taps + q] / a0 : (q == 0 ? 1.0 : 0.0);
+            }
+        zp = zi ? zi + (((long long)s * bands + band) * C + c) * (taps - 1) : nullptr;
+#pragma unroll
+        for (int q = 0; q < MAXT - 1; ++q)
+            if (q < taps - 1) z[q] = zp ? zp[q] : 0.0;
+    }
+    double* sblk = sq + (long long)s * C * Tn * bands;
+    for (int j = 0; j < k; ++j) {
+        const double* data = bins + ((long long)s * k + j) * C * Tn;
+        // 1. common average over the good channels, in channel order
+        for (int t = tid; t < Tn; t += nthr) {
+            double acc = 0.0;
+            for (int cc = 0; cc < C; ++cc)
+                if (!gs || gs[cc]) acc += data[(long long)cc * Tn + t];
+            avg[t] = acc / (double)ngood;
+        }
+        __syncthreads();
+        // 2. filters; a FIR (zi == NULL) starts every bin from a zero state, as the reference does
+        if (filt) {
+            if (!zp) {
+#pragma unroll
+                for (int q = 0; q < MAXT; ++q) z[q] = 0.0;
+            }
+            const double* xr = data + (long long)c * Tn;
+            double* yo = sblk + ((long long)c * Tn) * bands + band;
+            for (int t = 0; t < Tn; ++t) {
+                const double x = xr[t] - avg[t];
+                double y;
+                if (taps > 1) {
+                    y = z[0] + b[0] * x;
+                    // z[q] = z[q+1] + x b[q+1] - y a[q+1] for q < taps - 2, then z[taps-2] = x b[taps-1] - y a[taps-1]
+#pragma unroll
+                    for (int q = 0; q < MAXT - 1; ++q) {
+                        if (q < taps - 2) z[q] = z[q + 1] + x * b[q + 1] - y * a[q + 1];
+                        else if (q == taps - 2) z[q] = x * b[q + 1] - y * a[q + 1];
+                    }
+                } else {
+                    y = x * b[0];
+                }
+                yo[(long long)t * bands] = y * y;
+            }
+        }
+        __syncthreads();
+        // 3. RMS over the channel's contiguous (time, band) block of this bin
+        if (tid < HG_CPB && c0 + tid < C) {
+            const int n = Tn * bands;
+            power[((long long)s * k + j) * C + c0 + tid] = sqrt(np_pairwise_sum(sblk + (long long)(c0 + tid) * n, n) / (double)n);
+        }
+        __syncthreads();          // avg and the squared block are rewritten by the next bin
+    }
+    if (zp) {
+#pragma unroll
+        for (int q = 0; q < MAXT - 1; ++q)
+            if (q < taps - 1) zp[q] = z[q];
+    }
+}
+}  // namespace
+
+extern "C" size_t xps_pipe_frontend_f64_workspace(int n_streams, int C, int Tn, int bands) {
+    if (n_streams < 1 || C < 1 || Tn < 1 || bands < 1) return 16;
+    return (size_t)n_streams * C * Tn * bands * sizeof(double) + 16;
+}
+
+extern "C" int xps_pipe_frontend_f64(const double* bins, int n_streams, int k, int C, int Tn, const uint8_t* good,
+                                     const double* b, const double* a, int bands, int taps, double* zi, double* power,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    XPS_CHECK_ARG(bins && power && n_streams >= 1 && k >= 1 && C >= 1 && Tn >= 1, "bad argument");
+    XPS_CHECK_ARG(n_streams <= 8, "1..8 streams per call");
+    XPS_CHECK_ARG(Tn <= HG_MAXT, "bin longer than 2048 samples");
+    XPS_CHECK_ARG(b && bands >= 1 && bands <= 32 && taps >= 1 && taps <= HG_MAXTAPS, "1..32 bands of 1..32 filter taps");
+    XPS_CHECK_ARG(!zi || a, "a carried state needs IIR coefficients (a)");
+    if (!workspace || workspace_bytes < xps_pipe_frontend_f64_workspace(n_streams, C, Tn, bands)) {
+        xps_set_error("xps_pipe_frontend_f64: workspace too small");
+        return XPS_E_WORKSPACE;
+    }
+    const int threads = ((HG_CPB * bands + 63) / 64) * 64;
+#define LAUNCH(MT) hipLaunchKernelGGL(pipe_frontend_kernel<MT>, dim3(cdiv(C, HG_CPB), n_streams), dim3(threads), 0,      \
+                                      (hipStream_t)stream, bins, k, C, Tn, (const unsigned char*)good, b, a, bands, taps, zi, \
+                                      (double*)workspace, power);
+    if (taps <= 9) { LAUNCH(9) }                  // band-pass IIR up to order 4
+    else if (taps <= 17) { LAUNCH(17) }           // up to order 8
+    else { LAUNCH(HG_MAXTAPS) }
+#undef LAUNCH
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}

@@ -123,3 +123,89 @@ extern "C" int xps_gru_cell_gemv_f32(const float* x, int K, const float* w_ih, c
     XPS_CHECK_LAUNCH();
     return XPS_OK;
 }
+
+// ---- realtime pipeline glue (realtime_sim/realtime_pipeline.py) --------------------------------------------------------
+namespace {
+
+// dst[s] = src[s] shifted left by k frames, the k new frames float32(power[s][j] @ W[s] + c[s]) appended at the end.
+// One thread per window element; src and dst are different buffers (ping-pong), so no workgroup reads what another
+// writes.  W == NULL: identity (d == C), the frames are the cast powers.
+__global__ __launch_bounds__(256) void window_shift_kernel(const double* __restrict__ power, int k, int C,
+                                                           const double* __restrict__ W, const double* __restrict__ cvec,
+                                                           const float* __restrict__ src, float* __restrict__ dst,
+                                                           int win, int d) {
+    const int s = blockIdx.y;
+    const int K = win * d;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= K) return;
+    const int f = q / d, e = q % d;
+    float v;
+    if (f < win - k) {
+        v = src[(long long)s * K + q + k * d];
+    } else {
+        const double* p = power + ((long long)s * k + (f - (win - k))) * C;
+        if (W) {
+            const double* w = W + (long long)s * C * d + e;
+            double acc = 0.0;
+            for (int i = 0; i < C; ++i) acc += p[i] * w[(long long)i * d];
+            if (cvec) acc += cvec[(long long)s * d + e];
+            v = (float)acc;
+        } else {
+            v = (float)p[e];
+        }
+    }
+    dst[(long long)s * K + q] = v;
+}
+
+// Online greedy CTC collapse, one thread per stream: a = first maximum of the logits (torch.argmax); a token is appended when
+// a differs from the previous step's argmax and is not blank.  state[s] = {previous argmax (-1 before the first step),
+// token count, overflow flag}; plain per-lane stores.
+__global__ void ctc_collapse_kernel(const float* __restrict__ logits, int n_classes, int blank, long long* __restrict__ argmax,
+                                    int* __restrict__ state, long long* __restrict__ tokens, int max_tokens, int B) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= B) return;
+    const float* p = logits + (long long)s * n_classes;
+    float best = p[0];
+    int bi = 0;
+    for (int c = 1; c < n_classes; ++c)
+        if (p[c] > best) { best = p[c]; bi = c; }
+    argmax[s] = bi;
+    int* st = state + 3 * s;
+    const int prev = st[0];
+    st[0] = bi;
+    if (bi != prev && bi != blank) {
+        const int n = st[1];
+        if (n < max_tokens) {
+            tokens[(long long)s * max_tokens + n] = bi;
+            st[1] = n + 1;
+        } else {
+            st[2] = 1;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int xps_window_shift_f32(const double* power, int k, int C, const double* W, const double* c, const float* src,
+                                    float* dst, int win, int d, int B, void* stream) {
+    XPS_CHECK_ARG(power && src && dst && k >= 1 && C >= 1 && d >= 1 && win >= 1, "bad argument");
+    XPS_CHECK_ARG(B >= 1 && B <= MAXS, "1..8 streams per call");
+    XPS_CHECK_ARG(k <= win, "more new frames than the window holds");
+    XPS_CHECK_ARG(W || d == C, "the identity map needs d == C");
+    XPS_CHECK_ARG(src != dst, "dst must not alias src (other workgroups still read it)");
+    hipLaunchKernelGGL(window_shift_kernel, dim3(cdiv((long long)win * d, 256), B), dim3(256), 0, (hipStream_t)stream,
+                       power, k, C, W, c, src, dst, win, d);
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}
+
+extern "C" int xps_ctc_collapse_f32(const float* logits, int n_classes, int blank, int64_t* argmax, int32_t* state,
+                                    int64_t* tokens, int max_tokens, int B, void* stream) {
+    XPS_CHECK_ARG(logits && argmax && state && tokens && n_classes >= 1 && max_tokens >= 1, "bad argument");
+    XPS_CHECK_ARG(B >= 1 && B <= MAXS, "1..8 streams per call");
+    XPS_CHECK_ARG(blank >= 0 && blank < n_classes, "blank outside the classes");
+    hipLaunchKernelGGL(ctc_collapse_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, logits, n_classes, blank,
+                       (long long*)argmax, (int*)state, (long long*)tokens, max_tokens, B);
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}

@@ -1,2 +1,3 @@
 from .ctc_decoder import greedy_decode_batch  # noqa: F401
 from .realtime_nn_model import DenseClassifier, RealtimeRNNModel, StackedRNN, StreamingDecoder  # noqa: F401
+from .realtime_pipeline import RealtimePipeline, feature_map_from  # noqa: F401

@@ -297,6 +297,20 @@ int xps_gemv_f32(const float* x, const float* W, const float* bias, float* out, 
 int xps_gru_cell_gemv_f32(const float* x, int K, const float* w_ih, const float* w_hh, const float* b_ih,
                           const float* b_hh, const float* h_prev, float* h_new, int H, int B, void* stream);
 
+/* Realtime pipeline glue (realtime_sim/realtime_pipeline.py): the window of a stream is win frames of d floats, one
+ * contiguous row of win*d; rows [S][win*d] as above.
+ * xps_window_shift_f32: dst[s] = src[s] shifted left by k frames (1 <= k <= win), followed by the k new frames
+ *   float32(power[s][j] @ W[s] + c[s]) (power [B][k][C] float64, W [B][C][d] float64, c [B][d] float64 or NULL;
+ *   W == NULL: identity, d == C).  dst must not alias src (ping-pong pair).
+ * xps_ctc_collapse_f32: online greedy CTC collapse of one step.  argmax[b] = first maximum of logits[b] (torch.argmax);
+ *   state [B][3] int32 = {previous argmax (-1 before the first step), token count, overflow flag}; the argmax is
+ *   appended to tokens[b][0 .. max_tokens) when it differs from the previous one and is not `blank`, and the overflow flag
+ *   is set (sticky) instead when the row is full.  Counts and flags are the caller's to reset.                     */
+int xps_window_shift_f32(const double* power, int k, int C, const double* W, const double* c, const float* src,
+                         float* dst, int win, int d, int B, void* stream);
+int xps_ctc_collapse_f32(const float* logits, int n_classes, int blank, int64_t* argmax, int32_t* state,
+                         int64_t* tokens, int max_tokens, int B, void* stream);
+
 /* out[b][:] = table[idx[b]][:]  (embedding / precomputed input projection rows) */
 int xps_gather_rows_f32(const float* table, const int64_t* idx, float* out,
                         int B, int cols, int n_rows, void* stream);
@@ -443,6 +457,15 @@ size_t xps_process_hg_f64_workspace(int C, int Tn, int bands);
 int xps_process_hg_f64(const double* data, int C, int Tn, const uint8_t* good, const double* b, const double* a,
                        int bands, int taps, double* zi, int do_car, double* car_out, double* filtered,
                        double* power, void* workspace, size_t workspace_bytes, void* stream);
+/* The realtime pipeline's frontend: xps_process_hg_f64 (CAR over the good channels -> band-pass with carried state -> RMS)
+ * over k consecutive bins of n_streams (1..8) streams in one launch.  bins [n_streams][k][C][Tn], good [n_streams][C]
+ * (NULL: all good), b, a [bands][taps] as above (a == NULL: FIR, every bin from a zero state), zi [n_streams][bands][C][taps-1]
+ * carried from bin to bin and updated in place (IIR; NULL: zero state per bin), power [n_streams][k][C].  Bin j of stream s
+ * gives the bits of xps_process_hg_f64 on that bin alone with the state left by bin j-1. */
+size_t xps_pipe_frontend_f64_workspace(int n_streams, int C, int Tn, int bands);
+int xps_pipe_frontend_f64(const double* bins, int n_streams, int k, int C, int Tn, const uint8_t* good, const double* b,
+                          const double* a, int bands, int taps, double* zi, double* power, void* workspace,
+                          size_t workspace_bytes, void* stream);
 /* Y[r][:] = (X[r][:] - mean) @ Wt   X: n x d_in (float32 or float64), W: d_in x d_out float64,
  * Y float64 or float32.  Batched transform apply of every aligner.              */
 int xps_apply_f64(const void* X, int x_is_f32, int64_t ldx, const double* mean, const double* W,
