@@ -104,6 +104,11 @@ SIGNATURES = {
     'xps_next_token': (_i, [_vp, _i, _vp, _i64, _vp, _vp, _i, _vp]),
     'xps_window_shift_f32': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'xps_ctc_collapse_f32': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    'xps_ctc_beam_workspace': (_sz, [_i, _i, _i, _i]),
+    'xps_ctc_beam_f64': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'xps_ctc_beam_state_bytes': (_sz, [_i, _i, _i]),
+    'xps_ctc_beam_step_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
+    'xps_ctc_beam_readout': (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'xps_decoder_select_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'xps_dropout_f32': (_i, [_vp, _vp, _vp, _i64, _f, C.c_uint64, _vp]),
     'xps_split4_f32': (_i, [_vp, _vp, _i64, _f, C.c_uint64, _vp]),

@@ -1,5 +1,5 @@
 """Realtime CTC pipeline on the MI355X: raw ECoG bins of one or more patients -> high-gamma power -> alignment map ->
-sliding window -> GRU step -> greedy CTC tokens, one hipGraph replay per prediction.
+sliding window -> GRU step -> greedy (or prefix beam search) CTC tokens, one hipGraph replay per prediction.
 
 The reference runs these stages as separate host steps (realtime_sim/realtime_processing.py process_HG per bin, the
 PCA / CCA transforms of realtime_datamodule.py, the windowing of realtime_nn_model.py and ctc_decoder.py's greedy
@@ -10,6 +10,7 @@ decode).  Here one prediction is a linear chain of launches on one stream, captu
     xps_gru_cell_gemv_f32   x L (ping-pong hidden state, as StreamingDecoder)
     xps_gemv_f32            classifier
     xps_ctc_collapse_f32    argmax + online greedy collapse into a device token buffer
+    xps_ctc_beam_step_f32   decoder='beam' only: one frame of the prefix beam search, beam kept in device state
 
 Streams are different patients sharing one model: each has its own bad channels, alignment map and filter state; a patient
 with fewer electrodes is padded with bad channels and zero map rows.  There is no CPU fallback."""
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 from .._lib import call, lib
+from .ctc_decoder import check_beam_sizes
 from .realtime_nn_model import _layer_params
 from .realtime_processing import _good_mask, _split_coefs
 
@@ -74,11 +76,14 @@ def _per_stream(value, n_streams, is_single):
 
 
 class RealtimePipeline:
-    """Raw bins (n_streams, k, n_channels, bin_samples) float64 -> logits and greedy-CTC tokens per stream.  See the
-    module docstring for the launch chain; ``step`` replays one captured graph per prediction (``use_graph``)."""
+    """Raw bins (n_streams, k, n_channels, bin_samples) float64 -> logits and CTC tokens per stream.  See the module
+    docstring for the launch chain; ``step`` replays one captured graph per prediction (``use_graph``).
+    decoder='greedy' (default): ``decoded`` holds the greedy collapse.  decoder='beam': the prefix beam search of
+    realtime_sim.decode over the log-softmax of the logits, beam_size wide, advanced one frame per prediction on the
+    device; ``decoded`` / ``beam_nll`` read its best prefix (at most max_steps predictions between resets)."""
 
     def __init__(self, model, bandpassCoefs, n_channels, bin_samples, n_streams=1, bad_channels=None, filt_ics=None,
-                 feature_map=None, use_graph=True, max_tokens=4096):
+                 feature_map=None, use_graph=True, max_tokens=4096, decoder='greedy', beam_size=100, max_steps=4096):
         rnn = model.rnn.rnn
         if rnn.bidirectional:
             raise ValueError('the realtime pipeline needs a unidirectional model')
@@ -92,6 +97,8 @@ class RealtimePipeline:
             raise ValueError(f'win_size {self.win} < stride {self.stride}: frames would be skipped')
         if max_tokens < 1:
             raise ValueError('max_tokens must be >= 1')
+        if decoder not in ('greedy', 'beam'):
+            raise ValueError(f"decoder {decoder!r}: 'greedy' or 'beam'")
         self.model, self.B, self.dev, self._call = model, int(n_streams), dev, call
         self.C, self.Tn = int(n_channels), int(bin_samples)
         self.H, self.L, self.K = rnn.hidden_size, rnn.num_layers, rnn.input_size
@@ -156,6 +163,17 @@ class RealtimePipeline:
         self._token = torch.zeros(S, dtype=torch.int64, device=dev)
         self._state = torch.zeros(B, 3, dtype=torch.int32, device=dev)
         self._tokens = torch.zeros(B, self.max_tokens, dtype=torch.int64, device=dev)
+        self.decoder = decoder
+        if decoder == 'beam':
+            check_beam_sizes(int(beam_size), self.n_classes, self.blank)
+            if not 1 <= max_steps <= 1 << 20:
+                raise ValueError('max_steps outside 1..2^20')
+            self.beam_size, self.max_steps = int(beam_size), int(max_steps)
+            self._bstate_bytes = int(lib().xps_ctc_beam_state_bytes(B, self.beam_size, self.max_steps))
+            self._bstate = torch.zeros(self._bstate_bytes, dtype=torch.uint8, device=dev)
+            self._bprefix = torch.zeros(self.max_steps, dtype=torch.int64, device=dev)
+            self._blen = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._bnll = torch.zeros(1, dtype=torch.float64, device=dev)
         self._params = [tuple(p.detach().contiguous() for p in _layer_params(rnn, l, 1)[0]) for l in range(self.L)]
         self._fc = (model.classifier.fc.weight.detach().contiguous(), model.classifier.fc.bias.detach().contiguous())
         self.graphs = None
@@ -183,6 +201,8 @@ class RealtimePipeline:
         self.hbuf[:, :, :self.B] = self.model.h0.detach().expand(-1, self.B, -1)
         self._state.zero_()
         self._state[:, 0] = -1
+        if self.decoder == 'beam':
+            self._beam_headers().zero_()      # an all-zero header is the empty beam
         self._logits.zero_()
         self._token.zero_()
         self.parity, self.frames, self.n_pred, self._last_k = 0, 0, 0, 0
@@ -211,8 +231,32 @@ class RealtimePipeline:
         k = self._last_k                      # the frontend writes [n_streams][k][C] packed for the k of its launch
         return self._power.view(-1)[:self.B * k * self.C].view(self.B, k, self.C)
 
+    def _beam_headers(self):
+        """The int32 header {step, n_members, overflow, 0} of every stream's beam state (include/xps.h), (n_streams, 4)."""
+        return self._bstate.view(self.B, -1)[:, :16].view(torch.int32)
+
+    def _beam_readout(self, s):
+        if not 0 <= s < self.B:
+            raise IndexError(f'stream {s} of {self.B}')
+        if int(self._beam_headers()[s, 2]):
+            raise RuntimeError(f'stream {s} ran more than max_steps = {self.max_steps} beam-search steps')
+        self._call('xps_ctc_beam_readout', self._bstate.data_ptr(), self._bstate_bytes, self.B, self.beam_size,
+                   self.max_steps, s, self._bprefix.data_ptr(), self._blen.data_ptr(), self._bnll.data_ptr(),
+                   torch.cuda.current_stream().cuda_stream)
+        return self._bprefix[:int(self._blen)].clone()
+
+    def beam_nll(self, s):
+        """-log p of stream s's best beam prefix so far (float); raises after a max_steps overflow."""
+        if self.decoder != 'beam':
+            raise RuntimeError("beam_nll needs decoder='beam'")
+        self._beam_readout(s)
+        return float(self._bnll)
+
     def decoded(self, s):
-        """Greedy-CTC tokens of stream s so far (1-D LongTensor, device); raises after a token-buffer overflow."""
+        """CTC tokens of stream s so far (1-D LongTensor, device): the greedy collapse, or with decoder='beam' the beam's
+        best prefix; raises after a token-buffer (greedy) or max_steps (beam) overflow."""
+        if self.decoder == 'beam':
+            return self._beam_readout(s)
         if not 0 <= s < self.B:
             raise IndexError(f'stream {s} of {self.B}')
         _, n, over = (int(v) for v in self._state[s].cpu())
@@ -247,6 +291,9 @@ class RealtimePipeline:
                    self.n_classes, self.H, self.B, st)
         self._call('xps_ctc_collapse_f32', self._logits.data_ptr(), self.n_classes, self.blank, self._token.data_ptr(),
                    self._state.data_ptr(), self._tokens.data_ptr(), self.max_tokens, self.B, st)
+        if self.decoder == 'beam':
+            self._call('xps_ctc_beam_step_f32', self._logits.data_ptr(), self.n_classes, self.blank, self.beam_size,
+                       self.max_steps, self._bstate.data_ptr(), self._bstate_bytes, self.B, st)
 
     def _check_bins(self, bins, k):
         want = (self.B, k, self.C, self.Tn)

@@ -311,6 +311,28 @@ int xps_window_shift_f32(const double* power, int k, int C, const double* W, con
 int xps_ctc_collapse_f32(const float* logits, int n_classes, int blank, int64_t* argmax, int32_t* state,
                          int64_t* tokens, int max_tokens, int B, void* stream);
 
+/* CTC prefix beam search (realtime_sim/ctc_decoder.py), fp64, the reference decode's result and tie order.
+ * Sizes: 1 <= beam_size <= 128, 1 <= n_classes <= 64, beam_size * n_classes <= 8192, 0 <= blank < n_classes; else
+ * XPS_E_INVALID before any launch.
+ * ..._f64: the offline batch, one launch, one workgroup per sequence.  log_probs [B][T][n_classes] float32
+ *   (is_f32 = 1) or float64, input_lengths [B] int64 (NULL: all T; clamped to 0..T); from_logits = 1 applies a row-wise fp64 log-softmax first.
+ *   prefix [B][T] int64 gets the best prefix of each sequence (-1 after its end), prefix_len [B] int64 its length,
+ *   nll [B] float64 its -logsumexp(p_b, p_nb).  Workspace: ..._workspace bytes (backpointers).
+ * ..._step_f32: the streaming form.  Advances the beam of each of B (1..8) streams by one frame of float32
+ *   logits [B][n_classes] (always from_logits).  state: ..._state_bytes(B, beam_size, max_steps) bytes, one
+ *   block per stream starting with int32 {step, n_members, overflow, 0}; all zero = the empty beam (the caller's reset).
+ *   A step with step == max_steps sets the sticky overflow flag and leaves the beam as it is.  Graph-capturable.
+ * ..._readout: stream s's best prefix so far into prefix [max_steps] int64, its length and nll (one each). */
+size_t xps_ctc_beam_workspace(int B, int T, int beam_size, int n_classes);
+int xps_ctc_beam_f64(const void* log_probs, int is_f32, int B, int T, int n_classes, const int64_t* input_lengths,
+                     int blank, int beam_size, int from_logits, int64_t* prefix, int64_t* prefix_len, double* nll,
+                     void* workspace, size_t workspace_bytes, void* stream);
+size_t xps_ctc_beam_state_bytes(int n_streams, int beam_size, int max_steps);
+int xps_ctc_beam_step_f32(const float* logits, int n_classes, int blank, int beam_size, int max_steps, void* state,
+                          size_t state_bytes, int B, void* stream);
+int xps_ctc_beam_readout(const void* state, size_t state_bytes, int B, int beam_size, int max_steps, int s,
+                         int64_t* prefix, int64_t* prefix_len, double* nll, void* stream);
+
 /* out[b][:] = table[idx[b]][:]  (embedding / precomputed input projection rows) */
 int xps_gather_rows_f32(const float* table, const int64_t* idx, float* out,
                         int B, int cols, int n_rows, void* stream);

@@ -9,7 +9,10 @@ PCA -> CCA (d = 30); 1 and 4 streams.  Prints one JSON line.
 The reference's 2.06 ms per prediction (figure_analyses/supp/supp_fig_24.ipynb) was measured on other hardware and includes
 its host-side transform: context only.
 
-    python tools/realtime_latency.py [--n 2000] [--warmup 200]"""
+  --decoder beam --beam-size N: the pipeline also advances an N-wide CTC prefix beam search per prediction (one more
+           launch); --streams 1,4,8 picks the stream counts.
+
+    python tools/realtime_latency.py [--n 2000] [--warmup 200] [--decoder greedy|beam] [--beam-size 100] [--streams 1,4]"""
 import argparse
 import json
 import os
@@ -43,13 +46,13 @@ def _pca_cca(C, d):
     return feature_map_from(pca, cca)
 
 
-def measure(d, n_streams, n, warmup, fmap):
+def measure(d, n_streams, n, warmup, fmap, decoder='greedy', beam_size=100):
     from cross_patient_speech_decoding_amd.realtime_sim import RealtimePipeline, RealtimeRNNModel
     C, Tn, win, stride, H, L, ncls = 128, 40, 14, 4, 128, 2, 11
     torch.manual_seed(0)
     m = RealtimeRNNModel(win * d, H, L, ncls, dropout=0.0, win_size=win, stride=stride).cuda().eval()
     pipe = RealtimePipeline(m, _coefs(), C, Tn, n_streams=n_streams, feature_map=fmap, use_graph=True,
-                            max_tokens=1 << 16)
+                            max_tokens=1 << 16, decoder=decoder, beam_size=beam_size, max_steps=warmup + n + 256)
     rng = np.random.default_rng(1)
     src = rng.standard_normal((64, n_streams, stride, C, Tn))
     bins = torch.empty(n_streams, stride, C, Tn, dtype=torch.float64).pin_memory()
@@ -85,12 +88,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=2000)
     ap.add_argument('--warmup', type=int, default=200)
+    ap.add_argument('--decoder', choices=('greedy', 'beam'), default='greedy')
+    ap.add_argument('--beam-size', type=int, default=100)
+    ap.add_argument('--streams', default='1,4')
     a = ap.parse_args()
     torch.cuda.set_device(0)
     maps = {128: None, 30: _pca_cca(128, 30)}
-    rows = [measure(d, s, a.n, a.warmup, maps[d]) for d in (128, 30) for s in (1, 4)]
+    streams = [int(v) for v in a.streams.split(',')]
+    rows = [measure(d, s, a.n, a.warmup, maps[d], a.decoder, a.beam_size) for d in (128, 30) for s in streams]
     launches = 1 + 1 + 2 + 1 + 1               # frontend, map / shift, L = 2 GRU cells, classifier, collapse
+    launches += a.decoder == 'beam'            # beam step
     print(json.dumps({'tool': 'realtime_latency', 'shape': 'config5 C128 Tn40 bands8 order4 win14 stride4 H128 L2 cls11',
+                      'decoder': a.decoder, 'beam_size': a.beam_size if a.decoder == 'beam' else None,
                       'launches_per_prediction': launches, 'reference_ms_per_prediction': 2.06,
                       'reference_note': 'other hardware, includes the host transform: context only', 'rows': rows}))
 
