@@ -86,6 +86,7 @@ SIGNATURES = {
     'xps_gru_seq_bwd_split4_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _vp, _sz, _vp]),
     'xps_transpose_f32': (_i, [_vp, _vp, _i, _i, _vp]),
     'xps_transpose_batched_f32': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'xps_bn_centered_sumsq_f32': (_i, [_vp, _i, _i, _vp, _d, _vp, _vp, _sz, _vp]),
     'xps_bn_finalize_f32': (_i, [_vp, _d, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp]),
     'xps_bn_apply_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i64, _i, _i, _vp]),
     'xps_bn_finalize_apply_f32': (_i, [_vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _f, _vp, _i64, _i, _i, _vp]),

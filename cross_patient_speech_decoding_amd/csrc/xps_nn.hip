@@ -84,15 +84,53 @@ __global__ __launch_bounds__(1024) void colsum_stage2(const float* __restrict__ 
     }
 }
 
+// BatchNorm statistics in two passes over y (a one-pass sum(y^2)/n - mean^2 cancels once |mean| >> std: at
+// mean/std = 1000 and 40960 rows the fp32 sums lose about a quarter of rstd).  stats[0:F] = sum y (colsum);
+// stats[F:2F] = sum (y - mf)^2 about mf = float(sum y / count) (centered_sq_stage1 + colsum_stage2).  Both finalize
+// kernels and the centering pass take mf from bn_stats_mean, so they agree bit for bit; var = S2 / n - (m - mf)^2 is
+// the exact shifted-data identity.  Both halves are plain sums over rows: SyncBN all-reduces each half by sum.
+__device__ __forceinline__ double bn_stats_mean(const float* __restrict__ stats, double count, int c) {
+    return (double)stats[c] / count;
+}
+__device__ __forceinline__ double bn_stats_var(const float* __restrict__ stats, double count, int F, int c, double m) {
+    const double d = m - (double)(float)m;
+    double var = (double)stats[F + c] / count - d * d;
+    return var < 0 ? 0 : var;
+}
+
+// part[by][c] = sum over rows [by*RED_ROWS, ...) of (y - mf)^2, the same row split and fold order as colsum_stage1
+__global__ __launch_bounds__(256) void centered_sq_stage1(const float* __restrict__ X, int rows, int cols,
+                                                          const float* __restrict__ stats, double count,
+                                                          float* __restrict__ part) {
+    __shared__ float s2[4][64];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), rq = threadIdx.x >> 6;
+    const int r0 = blockIdx.y * RED_ROWS;
+    const int r1 = min(rows, r0 + RED_ROWS);
+    float a2 = 0.f;
+    if (c < cols) {
+        const float mf = (float)bn_stats_mean(stats, count, c);
+#pragma unroll 4
+        for (int r = r0 + rq; r < r1; r += 4) {
+            const float v = X[(long long)r * cols + c] - mf;
+            a2 += v * v;
+        }
+    }
+    s2[rq][threadIdx.x & 63] = a2;
+    __syncthreads();
+    if (rq == 0 && c < cols) {
+        const int l = threadIdx.x;
+        part[(long long)blockIdx.y * cols + c] = (s2[0][l] + s2[1][l]) + (s2[2][l] + s2[3][l]);
+    }
+}
+
 __global__ void bn_finalize_kernel(const float* __restrict__ stats, double count, float* mean, float* rstd,
                                    float* running_mean, float* running_var, long long* num_batches_tracked,
                                    float momentum, float eps, int F) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
     if (c >= F) return;
-    const double m = (double)stats[c] / count;
-    double var = (double)stats[F + c] / count - m * m;
-    if (var < 0) var = 0;
+    const double m = bn_stats_mean(stats, count, c);
+    const double var = bn_stats_var(stats, count, F, c, m);
     mean[c] = (float)m;
     rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (running_mean) {
@@ -128,9 +166,8 @@ __global__ void bn_finalize_apply_kernel(const float* __restrict__ y, const floa
     float* s_mean = bn_lds;
     float* s_rstd = bn_lds + F;
     for (int c = threadIdx.x; c < F; c += blockDim.x) {
-        const double m = (double)stats[c] / count;
-        double var = (double)stats[F + c] / count - m * m;
-        if (var < 0) var = 0;
+        const double m = bn_stats_mean(stats, count, c);
+        const double var = bn_stats_var(stats, count, F, c, m);
         const float mf = (float)m, rf = (float)(1.0 / sqrt(var + (double)eps));
         s_mean[c] = mf;
         s_rstd[c] = rf;
@@ -587,6 +624,24 @@ extern "C" int xps_colsum_f32(const float* X, int64_t ldx, int rows, int cols, f
     }
     hipLaunchKernelGGL(colsum_stage2, dim3(cdiv(cols, 64)), dim3(1024), 0, (hipStream_t)stream,
                        part, part_sq, nparts, cols, out, out_sq, accumulate);
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}
+
+extern "C" int xps_bn_centered_sumsq_f32(const float* y, int rows, int F, const float* stats, double count, float* out_sq,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    XPS_CHECK_ARG(y && stats && out_sq && rows >= 1 && F >= 1 && count > 0, "bad argument");
+    if (workspace_bytes < xps_colsum_f32_workspace(rows, F) || !workspace) {
+        xps_set_error("xps_bn_centered_sumsq_f32: workspace too small");
+        return XPS_E_WORKSPACE;
+    }
+    const int nparts = cdiv(rows, RED_ROWS);
+    float* part = (float*)workspace;
+    hipLaunchKernelGGL(centered_sq_stage1, dim3(cdiv(F, 64), nparts), dim3(256), 0, (hipStream_t)stream,
+                       y, rows, F, stats, count, part);
+    XPS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(colsum_stage2, dim3(cdiv(F, 64)), dim3(1024), 0, (hipStream_t)stream,
+                       part, (const float*)nullptr, nparts, F, out_sq, (float*)nullptr, 0);
     XPS_CHECK_LAUNCH();
     return XPS_OK;
 }

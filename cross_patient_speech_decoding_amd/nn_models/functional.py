@@ -847,12 +847,17 @@ class TemporalConvFn(torch.autograd.Function):
         gemm_nt(x, w2, y, rows, F, k * Cin, bias=conv_b, ra=ra, rc=rc)
         out = torch.empty_like(y)
         if training:
+            # two passes (BatchNorm statistics): sum y, then sum (y - mean)^2 about the global mean
             stats = torch.empty(2 * F, dtype=_f32, device=x.device)
-            colsum(y, rows, F, out=stats[:F], out_sq=stats[F:])
-            synced = _dist_sum_(stats, group)
+            nbytes = lib().xps_colsum_f32_workspace(rows, F)
+            ws = _ws(nbytes, x.device)
+            call('xps_colsum_f32', _ptr(y), F, rows, F, _ptr(stats), None, 0, _ptr(ws), nbytes, _stream())
             count = float(rows)
-            if synced:
+            if _dist_sum_(stats[:F], group):
                 count = _global_rows(rows, group, x.device, global_trials, Tp)
+            call('xps_bn_centered_sumsq_f32', _ptr(y), rows, F, _ptr(stats), count, _ptr(stats[F:]), _ptr(ws), nbytes,
+                 _stream())
+            _dist_sum_(stats[F:], group)
             mean = torch.empty(F, dtype=_f32, device=x.device)
             rstd = torch.empty(F, dtype=_f32, device=x.device)
             call('xps_bn_finalize_apply_f32', _ptr(y), _ptr(stats), count, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd),

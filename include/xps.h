@@ -234,9 +234,15 @@ int xps_transpose_batched_f32(const float* const* src, float* const* dst, int n,
 /* (nn_models/models.py:599-636).  The convolution itself is xps_gemm_nt_f32     */
 /* over window rows; these are the fused normalisation passes.                   */
 /*   y, out : [rows][F]  rows = T' * B                                           */
-/*   stats  : [2F] sum and sum of squares over rows (all-reduced by the caller    */
-/*            under data parallelism: SyncBN), count = global number of rows      */
+/*   stats  : [2F] stats[0:F] = sum of y over rows (xps_colsum_f32), then      */
+/*            stats[F:2F] = sum of (y - mf)^2, mf = float(stats[c] / count)       */
+/*            (xps_bn_centered_sumsq_f32); under data parallelism (SyncBN) the    */
+/*            caller all-reduces each half by sum before the next step;          */
+/*            count = global number of rows                                      */
 /* ------------------------------------------------------------------------- */
+/* second statistics pass: out_sq[c] = sum_r (y[r][c] - mf[c])^2, workspace of xps_colsum_f32_workspace(rows, F) */
+int xps_bn_centered_sumsq_f32(const float* y, int rows, int F, const float* stats, double count, float* out_sq,
+                              void* workspace, size_t workspace_bytes, void* stream);
 /* num_batches_tracked: device int64 counter (BatchNorm1d buffer) incremented by one, or NULL */
 int xps_bn_finalize_f32(const float* stats, double count, float* mean, float* rstd,
                         float* running_mean, float* running_var, int64_t* num_batches_tracked,

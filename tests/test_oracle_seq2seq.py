@@ -93,3 +93,75 @@ def test_state_dict_keys_are_the_reference_keys():
 def test_per_definition():
     assert phoneme_error_rate([[1, 2, 3]], [[1, 2, 3]]) == 0.0
     assert phoneme_error_rate([[1, 2, 3], [4, 5, 6]], [[1, 9, 3], [5, 6, 7]]) == pytest.approx(100 * 3 / 6)
+
+
+def _ones_masks(m, B, Tp):
+    F, H = m.temporal_conv.conv.out_channels, m.encoder.rnn.hidden_size
+    L, Ld = m.encoder.rnn.num_layers, m.decoder.rnn.num_layers
+    return {'conv': torch.ones(B, F, Tp, dtype=torch.float64), 'enc': [torch.ones(B, Tp, 2 * H, dtype=torch.float64)] * (L - 1),
+            'dec': [[torch.ones(B, H, dtype=torch.float64)] * (Ld - 1)] * m.seq_length}
+
+
+@pytest.mark.parametrize('name', ['tiny', 'tiny_relu_dec2', 'cfg2'])
+def test_all_ones_masks_give_the_unmasked_oracle(golden_dir, name):
+    """Explicit masks of ones at p = 0: the layer-by-layer GRUs give what nn.GRU gives, and the reference goldens hold."""
+    torch.set_num_threads(1)
+    g = np.load(os.path.join(golden_dir, f'seq2seq_{name}.npz'))
+    x, y = torch.from_numpy(g['x']), torch.from_numpy(g['y'])
+    m, sd = build(g)
+    m.eval()
+    cfg = ast.literal_eval(str(g['cfg']))
+    Tp = (x.shape[1] - cfg['kernel_size']) // cfg['stride'] + 1
+    with torch.no_grad():
+        plain = m(x, y, teacher_forcing_ratio=0)
+        m.double()
+        masked = m(x.double(), y, teacher_forcing_ratio=0, masks=_ones_masks(m, x.shape[0], Tp))
+    assert masked.dtype == torch.float64
+    np.testing.assert_allclose(masked.numpy(), plain.double().numpy(), rtol=0, atol=1e-6)
+    np.testing.assert_allclose(masked.numpy(), g['eval_logits'], rtol=0, atol=1e-6)
+    # a training step in float64 through the masked path against the reference's fp32 goldens
+    m2, _ = build(g)
+    m2.double()
+    opt, _ = m2.make_optimizer()
+    loss, logits = train_step(m2, opt, x.double(), y, coins=[True] * 3, clip=0.5, masks=_ones_masks(m2, x.shape[0], Tp))
+    np.testing.assert_allclose(loss.numpy(), g['tf1_loss'], rtol=1e-5)
+    np.testing.assert_allclose(logits.numpy(), g['tf1_logits'], atol=2e-6)
+
+
+@pytest.mark.parametrize('ndir,L', [(2, 2), (2, 3), (1, 3)])
+def test_masked_gru_is_per_layer_gru_with_the_mask_in_between(ndir, L):
+    """gru_masked == hand-composed one-layer nn.GRUs (copied weights) with x * mask / (1 - p) between them, forward and
+    backward, in float64; and it is not the undropped GRU."""
+    from oracle.seq2seq_oracle import gru_masked
+    torch.manual_seed(3)
+    B, T, In, H, p = 5, 7, 6, 8, 0.3
+    rnn = torch.nn.GRU(In, H, L, batch_first=True, dropout=p, bidirectional=ndir == 2).double()
+    x = torch.randn(B, T, In, dtype=torch.float64)
+    h0 = torch.randn(L * ndir, B, H, dtype=torch.float64)
+    masks = [(torch.rand(B, T, ndir * H) >= p).double() for _ in range(L - 1)]
+    assert all(0 < m.mean() < 1 for m in masks)
+    wt = torch.randn(B, T, ndir * H, dtype=torch.float64)
+    out, hn = gru_masked(rnn, x, h0, masks)
+    (out * wt).sum().backward()
+    inp, hs, layers = x, [], []
+    for l in range(L):
+        one = torch.nn.GRU(In if l == 0 else ndir * H, H, 1, batch_first=True, bidirectional=ndir == 2).double()
+        with torch.no_grad():
+            for sfx in [''] + (['_reverse'] if ndir == 2 else []):
+                for n in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh'):
+                    getattr(one, f'{n}_l0{sfx}').copy_(getattr(rnn, f'{n}_l{l}{sfx}'))
+        o, h = one(inp, h0[l * ndir:(l + 1) * ndir])
+        hs.append(h)
+        layers.append(one)
+        inp = o * masks[l] / (1 - p) if l < L - 1 else o
+    (inp * wt).sum().backward()
+    torch.testing.assert_close(out, inp, rtol=0, atol=1e-12)
+    torch.testing.assert_close(hn, torch.cat(hs, 0), rtol=0, atol=1e-12)
+    for l, one in enumerate(layers):
+        for sfx in [''] + (['_reverse'] if ndir == 2 else []):
+            for n in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh'):
+                torch.testing.assert_close(getattr(rnn, f'{n}_l{l}{sfx}').grad, getattr(one, f'{n}_l0{sfx}').grad,
+                                           rtol=0, atol=1e-11)
+    with torch.no_grad():
+        plain, _ = rnn(x, h0)
+    assert (plain - out).abs().max() > 1e-3                 # the masks did act
