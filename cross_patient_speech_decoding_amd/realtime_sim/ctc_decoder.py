@@ -12,8 +12,37 @@ from .._lib import call, lib
 BEAM_MAX, CLASSES_MAX, CANDIDATES_MAX = 128, 64, 8192
 
 
+def greedy_decode_device(scores, blank=0, time_major=False):
+    """Greedy CTC decode of a whole batch in ONE launch (xps_ctc_greedy_decode), no synchronisation.  scores: device tensor
+    (B, T, C), or (T, B, C) with time_major -- any strides over the first two axes (a permuted view is read in place),
+    float32 / float64 logits or log-probabilities.  Every frame is decoded.  Returns device tensors (tokens (B, T) int64:
+    the decoded labels of each sequence, then -1; lengths (B,) int64)."""
+    if scores.dim() != 3:
+        raise ValueError(f'scores of shape {tuple(scores.shape)}: expected three axes')
+    if not scores.is_cuda:
+        raise RuntimeError('cross_patient_speech_decoding_amd: greedy_decode_device needs a device tensor (no CPU fallback)')
+    if scores.dtype not in (torch.float32, torch.float64):
+        scores = scores.float() if scores.is_floating_point() else scores.double()
+    if scores.size(2) > 1 and scores.stride(2) != 1:
+        scores = scores.contiguous()
+    (T, B) = (scores.size(0), scores.size(1)) if time_major else (scores.size(1), scores.size(0))
+    st, sb = (scores.stride(0), scores.stride(1)) if time_major else (scores.stride(1), scores.stride(0))
+    Cn = scores.size(2)
+    if Cn < 1:
+        raise ValueError('greedy decode needs at least one class')
+    tokens = torch.empty(B, T, dtype=torch.int64, device=scores.device)
+    lengths = torch.empty(B, dtype=torch.int64, device=scores.device)
+    call('xps_ctc_greedy_decode', scores.data_ptr(), int(scores.dtype == torch.float32), int(st), int(sb), T, B, Cn, int(blank),
+         tokens.data_ptr(), lengths.data_ptr(), torch.cuda.current_stream(scores.device).cuda_stream)
+    return tokens, lengths
+
+
 def greedy_decode_batch(log_probs, blank=0):
-    """log_probs (B, T, C) -> list of 1-D LongTensors (on the input's device)."""
+    """log_probs (B, T, C) -> list of 1-D LongTensors (on the input's device).  A device tensor is decoded by the batched
+    kernel (one launch, one transfer of the B lengths); a host tensor by the reference's expression."""
+    if log_probs.is_cuda:
+        tokens, lengths = greedy_decode_device(log_probs, blank=blank)
+        return [tokens[b, :n] for b, n in enumerate(lengths.tolist())]
     best = log_probs.argmax(dim=2)
     keep = torch.ones_like(best, dtype=torch.bool)
     keep[:, 1:] = best[:, 1:] != best[:, :-1]

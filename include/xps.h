@@ -552,6 +552,41 @@ int xps_aug_scale_f32(const float* x, float* out, int64_t n, float scale, void* 
 int xps_aug_jitter_f32(const float* x, const float* noise, float* out, int64_t n, float level, void* stream);
 int xps_aug_time_warp_f32(const float* x, float* out, int N, int T, int C, int T2, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Cross-patient CTC training data (csrc/xps_ctc_data.hip)         */
+/* ------------------------------------------------------------------------- */
+/* Per-trial augmentations (realtime_sim/augmentations.py:14-90): ONE draw per trial, handed in as a DEVICE array of N
+ * entries made by the caller with the reference's generator calls.  x, out [N][T][C] fp32, single pass; `out` may point into
+ * a larger buffer (a slab of the concatenated training tensor); out != x for shift / warp.
+ *   trial_shift : out[n, t] = x[n, (t - shift[n]) mod T]      (:52-61; shift int64, any value)
+ *   trial_mask  : [start[n], start[n] + size) along time zeroed (:37-49; start int64; 0 <= size <= T, else XPS_E_INVALID;
+ *                 the part of a window that lies outside 0..T is ignored)
+ *   trial_scale : out[n] = x[n] * scale[n], one fp32 multiply   (:78-90; rows of row_len = T * C floats)
+ *   trial_warp  : two linear resamplings T -> T2[n] -> T, each ATen's upsample_linear1d with align_corners = False (source
+ *                 coordinate scale * (dst + 0.5) - 0.5 clamped at 0, neighbour index clamped at the end, fp32), fused: the
+ *                 intermediate row is never stored (:14-34; T2 int64 = int(T * factor[n]) computed by the caller, >= 1)
+ *   jitter      : element-wise already: xps_aug_jitter_f32 above                                     (:64-75)            */
+int xps_aug_trial_shift_f32(const float* x, float* out, int N, int T, int C, const int64_t* shift, void* stream);
+int xps_aug_trial_mask_f32(const float* x, float* out, int N, int T, int C, const int64_t* start, int size, void* stream);
+int xps_aug_trial_scale_f32(const float* x, float* out, int N, int64_t row_len, const float* scale, void* stream);
+int xps_aug_trial_warp_f32(const float* x, float* out, int N, int T, int C, const int64_t* T2, void* stream);
+/* Greedy CTC decode of a batch in one launch (realtime_sim/ctc_decoder.py:172-189): per frame the first maximum over the C
+ * classes (torch.argmax: lowest index on ties, the first NaN counts as the maximum), repeats collapsed, blanks dropped.
+ * logits: float32 (is_f32 = 1) or float64 scores or log-probabilities; frame t of sequence b starts at element
+ * t * stride_t + b * stride_b, its classes are contiguous -- (T, B, C) and (B, T, C) tensors both work.  Every one of the T
+ * frames is decoded.  tokens [B][T] int64: the decoded labels of sequence b, then -1; lengths [B] int64: their number. */
+int xps_ctc_greedy_decode(const void* logits, int is_f32, int64_t stride_t, int64_t stride_b, int T, int B, int C,
+                          int blank, int64_t* tokens, int64_t* lengths, void* stream);
+/* Unit-cost Levenshtein distance of B padded pairs in one launch (torchaudio.functional.edit_distance as used by calc_PER,
+ * realtime_sim/realtime_nn_model.py:307-324): pred [B][pred_stride] int64 with pred_len [B] int64, tgt [B][tgt_stride] int64 with
+ * tgt_len [B] int64 -> dist [B] int64.  max_pred_len / max_tgt_len: upper bounds of the lengths (<= the strides; a larger
+ * length entry is clamped to its bound).  Supported: max_pred_len <= 65536, max_tgt_len <= 1024
+ * (xps_edit_distance_supported); else XPS_E_INVALID before any launch. */
+int xps_edit_distance_supported(int max_pred_len, int max_tgt_len);
+int xps_edit_distance_i64(const int64_t* pred, int64_t pred_stride, const int64_t* pred_len, const int64_t* tgt,
+                          int64_t tgt_stride, const int64_t* tgt_len, int B, int max_pred_len, int max_tgt_len,
+                          int64_t* dist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
