@@ -143,6 +143,9 @@ SIGNATURES = {
     'xps_process_hg_f64': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'xps_pipe_frontend_f64_workspace': (_sz, [_i, _i, _i, _i]),
     'xps_pipe_frontend_f64': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'xps_hg_trials_f64_workspace': (_sz, [_i64, _i, _i, _i, _i]),
+    'xps_hg_trials_f64': (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i,
+                               _i, _vp, _vp, _sz, _vp]),
     'xps_aug_time_shift_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'xps_aug_time_mask_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'xps_aug_scale_f32': (_i, [_vp, _vp, _i64, _f, _vp]),

@@ -6,3 +6,5 @@ from .realtime_datamodule import (CTCDataset, CTCHeldOutDataModule, CTCHeldOutTa
 from .realtime_nn_model import (DenseClassifier, RealtimeRNNModel, StackedRNN, StreamingDecoder, calc_PER,  # noqa: F401
                                 edit_distance, edit_distance_device, per_device)
 from .realtime_pipeline import RealtimePipeline, feature_map_from  # noqa: F401
+from .realtime_processing import process_HG_trials  # noqa: F401
+from .session_replay import SessionReplay, SessionResult  # noqa: F401

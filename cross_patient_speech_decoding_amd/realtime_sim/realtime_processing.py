@@ -3,7 +3,9 @@ realtime_sim/realtime_processing.py (process_HG :10, CAR :42, filter_HG_bin :60,
 IIR_filter_HG_bin :106, compute_bin_power :146): same names, arguments and return values (numpy float64).
 
 Every function is one launch of the fused HIP kernel (xps_process_hg_f64: common average reference -> band-pass filters
-with carried state -> RMS); ``process_HG`` runs all three stages in a single launch.  The IIR path reproduces
+with carried state -> RMS); ``process_HG`` runs all three stages in a single launch and
+``process_HG_trials`` runs them over every bin of N recorded trials in one launch (xps_hg_trials_f64), bit for bit what
+looping ``process_HG`` over a trial's bins gives.  The IIR path reproduces
 scipy.signal.lfilter's direct-form-II-transposed arithmetic bit for bit (no fused multiply-add), the CAR and RMS stages
 numpy's summation order; the FIR path (scipy evaluates it with np.convolve / BLAS dot products, whose summation order
 is not defined) agrees to rounding.  There is no CPU fallback."""
@@ -138,3 +140,82 @@ def process_HG(data, bandpassCoefs, bad_channels=None, filt_ics=None):
     data = np.asarray(data, dtype=np.float64)
     b, a, z = _split_coefs(bandpassCoefs, data.shape[0], filt_ics)
     return _run(data, b, a, z, good=_good_mask(data.shape[0], bad_channels), do_car=True, want='power')
+
+
+def _hg_trials(raw, b, a, bands, taps, lengths=None, good=None, zi=None, want_state=False, want_power=True,
+               fmap=None, map_of_trial=None, n_maps=0):
+    """One xps_hg_trials_f64 launch on device tensors, no synchronisation.  raw (N, n_bins, C, Tn) float32 / float64
+    contiguous; b, a (bands, taps) float64 (a None: FIR); lengths (N,) int64 or None; good (C,) or (N, C) uint8 or None;
+    zi (bands, C, taps-1) or (N, bands, C, taps-1) or None; fmap None (no features), (None, None, d) for the identity
+    cast or (W (n_maps, C, d), c (n_maps, d) or None, d); map_of_trial (N,) int32 or None, checked by the kernel against
+    n_maps (W's, or the argument under the identity map): a trial with an index outside gets NaN features.
+    Returns (power or None, state or None, features or None)."""
+    N, n_bins, Cn, Tn = raw.shape
+    dev = raw.device
+    power = torch.empty(N, n_bins, Cn, dtype=_F64, device=dev) if want_power else None
+    state = torch.empty(N, bands, Cn, taps - 1, dtype=_F64, device=dev) if want_state else None
+    W = c = feats = None
+    d = 0
+    if fmap is not None:
+        W, c, d = fmap
+        n_maps = n_maps if W is None else W.shape[0]
+        feats = torch.empty(N, n_bins, d, dtype=torch.float32, device=dev)
+    nbytes = int(lib().xps_hg_trials_f64_workspace(N, n_bins, Cn, Tn, bands))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    call('xps_hg_trials_f64', raw.data_ptr(), int(raw.dtype == torch.float32), N, n_bins, Cn, Tn, ptr(lengths), ptr(good),
+         int(good is not None and good.dim() == 2), ptr(b), ptr(a), bands, taps, ptr(zi), int(zi is not None and zi.dim() == 4),
+         ptr(state), ptr(power), ptr(W), ptr(c), ptr(map_of_trial), n_maps, d, ptr(feats), ws.data_ptr(), nbytes,
+         torch.cuda.current_stream(dev).cuda_stream)
+    return power, state, feats
+
+
+def _check_trials(data, n_chan=None, bin_samples=None):
+    """(N, n_bins, C, Tn) tensor with no empty axis (and the given C, Tn), or ValueError with the shape."""
+    data = torch.as_tensor(data)
+    if data.dim() != 4 or 0 in data.shape or (n_chan is not None and (data.shape[2], data.shape[3]) != (n_chan, bin_samples)):
+        want = '(N, n_bins, n_channels, bin_samples)' if n_chan is None else f'(N, n_bins, {n_chan}, {bin_samples})'
+        raise ValueError(f'trials of shape {tuple(data.shape)}: expected {want}, no empty axis')
+    return data
+
+
+def _trials_on_device(data, n_chan=None, bin_samples=None):
+    """Checked trials, host or device, float32 or float64 (anything else is widened to float64) -> contiguous device tensor."""
+    data = _check_trials(data, n_chan, bin_samples)
+    if data.dtype not in (torch.float32, torch.float64):
+        data = data.to(_F64)
+    return data.to(_dev()).contiguous()
+
+
+def _trial_lengths(lengths, N, n_bins):
+    """lengths (N,) -> host int64 tensor, checked against 0..n_bins (None stays None)."""
+    if lengths is None:
+        return None
+    lens = torch.as_tensor(lengths).to('cpu', torch.int64).reshape(-1)
+    if lens.numel() != N:
+        raise ValueError(f'lengths of shape {tuple(torch.as_tensor(lengths).shape)} for {N} trials')
+    if int(lens.min()) < 0 or int(lens.max()) > n_bins:
+        raise ValueError(f'lengths outside 0..{n_bins}')
+    return lens
+
+
+def process_HG_trials(data, bandpassCoefs, bad_channels=None, filt_ics=None, lengths=None, return_state=False):
+    """process_HG over every bin of N trials in ONE launch: data (N, n_bins, channels, time) host or device, float32 or
+    float64 -> device float64 (N, n_bins, channels); row j of trial n is process_HG of that bin with the filter state bin
+    j - 1 left (bin 0: ``filt_ics`` (bands, channels, order), or one per trial (N, bands, channels, order); default
+    lfilter_zi tiled over the channels).  ``lengths`` (N,): trial n has that many bins, the rows after them are zeros.
+    ``return_state``: also the state after each trial's last bin, (N, bands, channels, order) (None for FIR).  The data
+    makes no host round trip."""
+    data = _check_trials(data)
+    N, n_bins, Cn, _ = data.shape
+    b, a, zi = _split_coefs(bandpassCoefs, Cn, filt_ics)
+    bands, taps = b.shape
+    if a is not None and zi.shape not in ((bands, Cn, taps - 1), (N, bands, Cn, taps - 1)):
+        raise ValueError(f'filt_ics of shape {zi.shape}: expected {(bands, Cn, taps - 1)} or {(N, bands, Cn, taps - 1)}')
+    lens = _trial_lengths(lengths, N, n_bins)
+    raw = _trials_on_device(data)
+    dev = raw.device
+    good = torch.from_numpy(_good_mask(Cn, bad_channels)).to(dev)
+    power, state, _ = _hg_trials(raw, _up(b), _up(a), bands, taps, None if lens is None else lens.to(dev), good,
+                                 None if a is None else _up(zi), want_state=return_state and a is not None)
+    return (power, state) if return_state else power

@@ -494,6 +494,26 @@ size_t xps_pipe_frontend_f64_workspace(int n_streams, int C, int Tn, int bands);
 int xps_pipe_frontend_f64(const double* bins, int n_streams, int k, int C, int Tn, const uint8_t* good, const double* b,
                           const double* a, int bands, int taps, double* zi, double* power, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* Session replay (realtime_sim/session_replay.py): the frontend over N recorded trials in one launch.
+ *   raw [N][n_bins][C][Tn] float64, or float32 (raw_is_f32 = 1) widened on load; bins_per_trial [N] int64 (NULL: n_bins;
+ *   clamped to 0..n_bins): trial n has that many bins, the rows after them are written as zeros.
+ *   good [C] or (good_per_trial = 1) [N][C], NULL: all good.  b, a [bands][taps] as above (a == NULL: FIR, no carried state).
+ *   zi0 [bands][C][taps-1] or (zi_per_trial = 1) [N][bands][C][taps-1], NULL: zero; zi_out [N][bands][C][taps-1] or NULL.
+ *   power [N][n_bins][C] or NULL: row j of trial n has the bits xps_pipe_frontend_f64 gives bin j of a stream that started
+ *   from zi0 and was fed bins 0..j of the trial; zi_out[n] that stream's state after the trial's last bin.
+ *   features [N][n_bins][d] float32 or NULL: float32(power[n][j] @ W[m] + c[m]) with m = map_of_trial[n] (NULL: 0), summed
+ *   as xps_window_shift_f32 sums it; W [n_maps][C][d], c [n_maps][d] or NULL; W == NULL: identity, d == C.  A map index
+ *   outside 0..n_maps-1 gives NaN rows (map_of_trial may be given with W == NULL, only to be checked against n_maps).
+ *   ..._workspace cannot know which outputs are asked for, so it always holds N*n_bins*C doubles (the power, used when
+ *   power == NULL) plus, for bands != 8, N*C*Tn*bands doubles (the squared bin of every trial).
+ * Tn <= 2048, 1 <= bands, taps <= 32, 1 <= N < 2^31; offsets are 64-bit.  bands == 8 sums in registers; other band counts
+ * go through the workspace.  Nothing synchronises. */
+size_t xps_hg_trials_f64_workspace(int64_t N, int n_bins, int C, int Tn, int bands);
+int xps_hg_trials_f64(const void* raw, int raw_is_f32, int64_t N, int n_bins, int C, int Tn,
+                      const int64_t* bins_per_trial, const uint8_t* good, int good_per_trial, const double* b,
+                      const double* a, int bands, int taps, const double* zi0, int zi_per_trial, double* zi_out,
+                      double* power, const double* W, const double* c, const int32_t* map_of_trial, int n_maps, int d,
+                      float* features, void* workspace, size_t workspace_bytes, void* stream);
 /* Y[r][:] = (X[r][:] - mean) @ Wt   X: n x d_in (float32 or float64), W: d_in x d_out float64,
  * Y float64 or float32.  Batched transform apply of every aligner.              */
 int xps_apply_f64(const void* X, int x_is_f32, int64_t ldx, const double* mean, const double* W,
