@@ -168,6 +168,12 @@ SIGNATURES = {
     'xps_lanczos_f64': (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'xps_cheb_filter_f64_workspace': (_sz, [_i, _i]),
     'xps_cheb_filter_f64': (_i, [_vp, _i64, _i, _vp, _i, _i, _d, _d, _d, _vp, _vp, _sz, _vp]),
+    'xps_group_mean_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    'xps_group_mean_f64': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    'xps_group_mean_many_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'xps_group_mean_many_f64': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'xps_select_channels_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    'xps_select_channels_f64': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
 }
 
 

@@ -607,6 +607,43 @@ int xps_edit_distance_i64(const int64_t* pred, int64_t pred_stride, const int64_
                           int64_t tgt_stride, const int64_t* tgt_len, int B, int max_pred_len, int max_tgt_len,
                           int64_t* dist, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Electrode subsampling (csrc/xps_subsample.hip): spatial        */
+/* averaging over groups of grid channels and channel selection, for one          */
+/* grouping or a whole sweep of them in one launch.                                */
+/* ------------------------------------------------------------------------- */
+/* processing_utils/spatial_avg_subsampling.py:74-90 (spatial_avg_data).  data [N][C][T]: the reference's (trials, X, Y, T)
+ * with the grid flattened row-major, C = X * Y.  Groups in CSR form: offsets[G + 1] (offsets[0] = 0) and members[offsets[G]],
+ * int32 channel numbers in [0, C), every group non-empty, groups may be ragged and may share channels (DEVICE arrays; the
+ * caller validates them: the library cannot read them without synchronising).  out [N][T][G] float64, channel-last.
+ * Arithmetic = np.mean(data[:, ix, iy], axis=1): the members of a group added one by one in member order in the INPUT's
+ * dtype, one division by the member count in that dtype, then widened to float64; no fused multiply-add, no atomics, the
+ * bits do not depend on the launch geometry.  XPS_E_INVALID when the C channels of one time sample exceed the LDS tile
+ * (C > 6144 for f32, C > 3072 for f64). */
+int xps_group_mean_f32(const float* data, int N, int C, int T, const int32_t* offsets, const int32_t* members, int G,
+                       double* out, void* stream);
+int xps_group_mean_f64(const double* data, int N, int C, int T, const int32_t* offsets, const int32_t* members, int G,
+                       double* out, void* stream);
+/* S groupings in ONE launch (CSR of CSR): grouping s owns the groups group_start[s] .. group_start[s + 1] - 1 (int32
+ * [S + 1], group_start[0] = 0, group_start[S] = Gtot) of the shared offsets[Gtot + 1] / members arrays.  out: one buffer of
+ * N * T * Gtot float64; the slab of grouping s starts at element N * T * group_start[s] and is [N][T][G_s].  Every staged
+ * input tile serves all S groupings before the next is loaded: the input is read from HBM once per launch.  Each slab
+ * holds the bits xps_group_mean_* gives for that grouping alone. */
+int xps_group_mean_many_f32(const float* data, int N, int C, int T, const int32_t* group_start, const int32_t* offsets,
+                            const int32_t* members, int S, int Gtot, double* out, void* stream);
+int xps_group_mean_many_f64(const double* data, int N, int C, int T, const int32_t* group_start, const int32_t* offsets,
+                            const int32_t* members, int S, int Gtot, double* out, void* stream);
+/* X[:, :, idx_s] for S index lists in one launch (scripts/aligned_decode_grid_subsample.py slices the channel-last features
+ * of every sliding window this way).  x [N][T][C] fp32; list s is idx[list_start[s] .. list_start[s + 1] - 1] (int32 device
+ * arrays, list_start[0] = 0, list_start[S] = Ltot, entries in [0, C)); out: N * T * Ltot fp32, slab s at element
+ * N * T * list_start[s], [N][T][L_s], the input's bits.  XPS_E_INVALID for C > 12288 (the channels of one sample exceed the
+ * LDS tile). */
+int xps_select_channels_f32(const float* x, int N, int T, int C, const int32_t* list_start, const int32_t* idx, int S,
+                            int Ltot, float* out, void* stream);
+/* the same for float64 features (C <= 6144) */
+int xps_select_channels_f64(const double* x, int N, int T, int C, const int32_t* list_start, const int32_t* idx, int S,
+                            int Ltot, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
