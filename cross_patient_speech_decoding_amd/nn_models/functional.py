@@ -8,6 +8,7 @@ Internal activation layout is TIME-MAJOR: (T, B, features).
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -64,6 +65,24 @@ def _ptr_array(tensors):
     return arr
 
 
+_memo_values = {}
+
+
+def _memo(key, compute):
+    """compute() once per key, for answers of the library that depend on nothing but the key: each use names in its key all
+    they depend on, library state (precision, cluster mode, BPTT grid) included.  Bounded: beyond 4096 keys nothing more is
+    kept.  _memo.clear() forgets everything."""
+    v = _memo_values.get(key)
+    if v is None:
+        v = compute()
+        if len(_memo_values) < 4096:
+            _memo_values[key] = v
+    return v
+
+
+_memo.clear = _memo_values.clear
+
+
 # --------------------------------------------------------------------------- #
 # raw GEMM wrappers                                                            #
 # --------------------------------------------------------------------------- #
@@ -107,9 +126,6 @@ def tn_problem(A, B, out, M, N, K, ra=None, rb=None, rc=None, colsum_out=None, a
                      rc or rowmap(N), M, N, K, int(bool(accumulate)) | (2 if accumulate_colsum else 0))
 
 
-_tn_ws_bytes = {}
-
-
 def gemm_tn_grouped(problems, device, stream=None):
     """All problems in ONE split-K launch + ONE reduce launch (deterministic).  stream: raw HIP stream handle to launch
     on (default: torch's current stream); returns the workspace tensors (the caller of a foreign-stream launch keeps them
@@ -119,12 +135,8 @@ def gemm_tn_grouped(problems, device, stream=None):
     for i in range(0, len(problems), 12):
         chunk = problems[i:i + 12]
         arr = (TnProblem * len(chunk))(*chunk)
-        key = tuple((q.M, q.N, q.K, bool(q.colsum_a)) for q in chunk)        # the slab layout depends on the shapes only
-        nbytes = _tn_ws_bytes.get(key)
-        if nbytes is None:
-            nbytes = lib().xps_gemm_tn_grouped_f32_workspace(arr, len(chunk))
-            if len(_tn_ws_bytes) < 1024:
-                _tn_ws_bytes[key] = nbytes
+        key = ('tn_ws', *[(q.M, q.N, q.K, bool(q.colsum_a)) for q in chunk])   # the slab layout depends on the shapes only
+        nbytes = _memo(key, lambda: lib().xps_gemm_tn_grouped_f32_workspace(arr, len(chunk)))
         ws = _ws(nbytes, device)
         call('xps_gemm_tn_grouped_f32', arr, len(chunk), _ptr(ws), nbytes, st)
         keep.append(ws)
@@ -200,6 +212,18 @@ def _grad_target(param, shape, device):
     return t, False, t
 
 
+def _grad_targets(w, w_shape, b, b_shape, device):
+    """_grad_target of a weight and of its bias, which one grouped-TN problem writes under ONE accumulate flag: both straight
+    into .grad, else both into temporaries.  Returns dw, db, accumulate, rw, rb (rw / rb: what autograd gets)."""
+    dw, acc_w, rw = _grad_target(w, w_shape, device)
+    db, acc_b, rb = _grad_target(b, b_shape, device)
+    if acc_w != acc_b:
+        dw = rw = torch.empty(w_shape, dtype=_f32, device=device)
+        db = rb = torch.empty(b_shape, dtype=_f32, device=device)
+        acc_w = False
+    return dw, db, acc_w, rw, rb
+
+
 def colsum(X, rows, cols, out=None, out_sq=None, ldx=None, accumulate=False):
     out = out if out is not None else torch.empty(cols, dtype=_f32, device=X.device)
     nbytes = lib().xps_colsum_f32_workspace(rows, cols)
@@ -254,14 +278,10 @@ class LinearFn(torch.autograd.Function):
                 dx = dx.view(ctx.xshape)
         need_w, need_b = ctx.needs_input_grad[1], b is not None and ctx.needs_input_grad[2]
         if need_w or need_b:
-            dw, acc_w, rw = _grad_target(w, (N, K), dy.device)
-            db = acc_b = None
             if need_b:
-                db, acc_b, rb = _grad_target(b, (N,), dy.device)
-                if acc_b != acc_w:                      # one accumulate flag per problem: fall back to temporaries
-                    dw = torch.empty(N, K, dtype=_f32, device=dy.device)
-                    db = torch.empty(N, dtype=_f32, device=dy.device)
-                    acc_w, rw, rb = False, dw, db
+                dw, db, acc_w, rw, rb = _grad_targets(w, (N, K), b, (N,), dy.device)
+            else:
+                (dw, acc_w, rw), db = _grad_target(w, (N, K), dy.device), None
             prob = [tn_problem(dy2, x2, dw, N, K, M, colsum_out=db, accumulate=acc_w)]
             _launch_weight_grads(lambda st: gemm_tn_grouped(prob, dy.device, st), dy.device, (dy2, x2),
                                  rw is None and (rb is None or not need_b))
@@ -277,18 +297,10 @@ def linear(x, w, b=None):
 # --------------------------------------------------------------------------- #
 # GRU                                                                          #
 # --------------------------------------------------------------------------- #
-_gru_ws_cache = {}
-
-
 def _gru_ws_bytes(fn, T, B, H, ndir):
     """Workspace size of the recurrence entry points (depends on the shape, the cluster mode and the BPTT grid only)."""
     key = (fn, T, B, H, ndir, lib().xps_get_gru_cluster_mode(), lib().xps_get_gru_bptt_grid())
-    n = _gru_ws_cache.get(key)
-    if n is None:
-        n = getattr(lib(), fn)(T, B, H, ndir)
-        if len(_gru_ws_cache) < 1024:
-            _gru_ws_cache[key] = n
-    return n
+    return _memo(key, lambda: getattr(lib(), fn)(T, B, H, ndir))
 
 
 # The cluster-persistent recurrence (256 < H <= 512) bounds every in-kernel wait; a wait that gave up stores 1 into ONE small
@@ -327,34 +339,19 @@ def set_gru_cluster_mode(name):
     call('xps_set_gru_cluster_mode', modes[name])
 
 
-_fused_drop_ok = {}
-
-
 def fused_dropout_supported(T, B, H, ndir):
-    """The recurrence kernels of this shape apply the inter-layer dropout themselves (XPS_FUSED_DROPOUT=0: never)."""
-    key = (T, B, H, ndir)
-    v = _fused_drop_ok.get(key)
-    if v is None:
-        v = os.environ.get('XPS_FUSED_DROPOUT', '1') != '0' and bool(lib().xps_gru_seq_fused_dropout_supported(T, B, H, ndir))
-        if len(_fused_drop_ok) < 256:
-            _fused_drop_ok[key] = v
-    return v
-
-
-_split4_ok = {}
+    """The recurrence kernels of this shape apply the inter-layer dropout themselves (XPS_FUSED_DROPOUT=0: never; the switch
+    is read when a shape is first asked about: _memo.clear() after changing it)."""
+    return _memo(('fused_drop', T, B, H, ndir), lambda: os.environ.get('XPS_FUSED_DROPOUT', '1') != '0'
+                 and bool(lib().xps_gru_seq_fused_dropout_supported(T, B, H, ndir)))
 
 
 def split4_supported(T, B, H, ndir):
     """The BPTT kernels of this shape can write dgi / dghn as XPS_FMT_SPLIT4 groups (include/xps.h) in the current precision
     mode: their readers (weight-gradient and input-gradient GEMMs) then stage them without conversion arithmetic, same bits.
-    XPS_SPLIT4=0: never."""
-    key = (T, B, H, ndir, lib().xps_get_gemm_precision(), lib().xps_get_gru_cluster_mode())
-    v = _split4_ok.get(key)
-    if v is None:
-        v = os.environ.get('XPS_SPLIT4', '1') != '0' and bool(lib().xps_gru_seq_bwd_split4_supported(T, B, H, ndir))
-        if len(_split4_ok) < 256:
-            _split4_ok[key] = v
-    return v
+    XPS_SPLIT4=0: never (read when a shape is first asked about in a library state: _memo.clear() after changing it)."""
+    key = ('split4', T, B, H, ndir, lib().xps_get_gemm_precision(), lib().xps_get_gru_cluster_mode())
+    return _memo(key, lambda: os.environ.get('XPS_SPLIT4', '1') != '0' and bool(lib().xps_gru_seq_bwd_split4_supported(T, B, H, ndir)))
 
 
 def split4_wanted(T, B, H, ndir):
@@ -365,23 +362,16 @@ def split4_wanted(T, B, H, ndir):
     return H > 256 and split4_supported(T, B, H, ndir)
 
 
-_saved_layout = {}
-
-
-def _stamp_saved(saved, B, H):
+def _launch_form(B, H):
     """The saved-gates buffer is private between the forward and the BPTT kernels and its layout depends on the launch form
-    (member-major on the cluster path, row-major on the single-workgroup path: csrc/xps_gru_cluster.hip): remember which form
-    wrote `saved`, so that a mode change between forward and backward is an error instead of silently wrong gradients."""
-    if saved is None:
-        return
-    if len(_saved_layout) > 4096:
-        _saved_layout.clear()
-    _saved_layout[saved.data_ptr()] = (lib().xps_get_gru_cluster_mode() != 0, B, H)
+    (member-major on the cluster path, row-major on the single-workgroup path: csrc/xps_gru_cluster.hip).  The form that wrote
+    `saved` travels with the forward -- on the autograd ctx, and as `saved.launch_form` for callers of _gru_forward -- so that a
+    mode change between forward and backward is an error instead of silently wrong gradients."""
+    return (lib().xps_get_gru_cluster_mode() != 0, B, H)
 
 
-def _check_saved(saved, B, H):
-    was = _saved_layout.get(saved.data_ptr())
-    now = (lib().xps_get_gru_cluster_mode() != 0, B, H)
+def _check_form(was, B, H):
+    now = _launch_form(B, H)
     if was is not None and was != now:
         raise RuntimeError(f'GRU backward: the saved gates were written with cluster path {"on" if was[0] else "off"} (B, H = {was[1:]}) '
                            f'but the backward runs with it {"on" if now[0] else "off"} (B, H = {now[1:]}): the launch form '
@@ -392,7 +382,8 @@ def _gru_forward(gi, w_hh, b_hh, h0, T, B, H, ndir, save, drop=None):
     dev = gi.device
     y_ext = torch.empty(T + 2, B, ndir * H, dtype=_f32, device=dev)
     saved = torch.empty(ndir, T, B, 4 * H, dtype=_f32, device=dev) if save else None
-    _stamp_saved(saved, B, H)
+    if save:
+        saved.launch_form = _launch_form(B, H)
     nbytes = _gru_ws_bytes('xps_gru_seq_fwd_f32_workspace', T, B, H, ndir)
     ws = _ws(nbytes, dev)
     if nbytes > 16:
@@ -408,32 +399,34 @@ def _gru_forward(gi, w_hh, b_hh, h0, T, B, H, ndir, save, drop=None):
     return y_ext, saved
 
 
-def hprev_split_wanted(T, B, H, ndir):
+def hprev_split_wanted(T, B, H, ndir, split4=None):
     """The weight-gradient group of a large layer (256 < H <= 512, bf16x3 mode: where dgi / dghn are XPS_FMT_SPLIT4 operands and the
     256-tile kernels run) reads h_prev from an XPS_FMT_SPLIT4 image of the state sequence, made by one pass on the stream that
     carries the group: with BOTH operands split the dW_hh products take the LDS-DMA k loop (csrc/xps_gemm_dma.h) -- the group of
-    configs[3]'s layer 1 1.07-1.2 ms -> 0.95 ms (tools/bench_wgrad_group.py) for a 0.37-GB pass.  XPS_HPREV_SPLIT=0: never."""
-    return (split4_wanted(T, B, H, ndir) and (ndir * H) % 4 == 0 and T * B >= 4096 and H % 256 == 0
+    configs[3]'s layer 1 1.07-1.2 ms -> 0.95 ms (tools/bench_wgrad_group.py) for a 0.37-GB pass.  XPS_HPREV_SPLIT=0: never.
+    split4: split4_wanted of this shape, where the caller has it (gru_layer_plan)."""
+    return ((split4_wanted(T, B, H, ndir) if split4 is None else split4) and (ndir * H) % 4 == 0 and T * B >= 4096 and H % 256 == 0
             and os.environ.get('XPS_HPREV_SPLIT', '1') != '0' and os.environ.get('XPS_GEMM_DMA', '1') != '0')
 
 
-def fwd_ysplit_wanted(T, B, H, ndir):
+def fwd_ysplit_wanted(T, B, H, ndir, hprev=None):
     """The forward recurrence launch writes the XPS_FMT_SPLIT4 image of y_ext that the weight-gradient group reads h_prev from
     (hprev_split_wanted) where the launch can use that image AS its in-kernel exchange buffer (xps_gru_seq_fwd_image_exchange_supported:
     H = 512, no pad trials): the image replaces the ring buffer's stores, and the xps_split4_f32 pass over y_ext in the backward
-    (65 us and 0.34 GB per layer at configs[3]'s shape) is gone.  XPS_FWD_YSPLIT=0: the pass."""
-    return (os.environ.get('XPS_FWD_YSPLIT', '1') != '0' and hprev_split_wanted(T, B, H, ndir)
+    (65 us and 0.34 GB per layer at configs[3]'s shape) is gone.  XPS_FWD_YSPLIT=0: the pass.  hprev: hprev_split_wanted of this
+    shape, where the caller has it."""
+    return (os.environ.get('XPS_FWD_YSPLIT', '1') != '0' and (hprev_split_wanted(T, B, H, ndir) if hprev is None else hprev)
             and bool(lib().xps_gru_seq_fwd_image_exchange_supported(T, B, H, ndir)))
 
 
-def fwd_images_wanted(T, B, H, ndir):
+def fwd_images_wanted(T, B, H, ndir, hprev=None):
     """OPT-IN (XPS_FWD_IMAGES=1): the forward launch ALSO writes the image of dropout(y) for a layer whose dropped output feeds the
     next layer's GEMMs (layer_output_split4_ok) -- and, off the image-exchange shapes, the image of y_ext as an extra store --
     instead of xps_split4_f32 passes over the finished tensors.  Bit-identical (tests/test_gpu_split4.py), measured level (round 4,
     serial profile: split4 passes 192 -> 0 us, forward kernels 1359 -> 1541 us per step; headline 6.60 vs 6.61 ms): an extra 1-KiB
     store instruction per gate wave and round goes through the per-CU vector-memory pipe that paces the cluster kernels,
-    at the price the separate pass pays at HBM speed.  Not the default."""
-    return (os.environ.get('XPS_FWD_IMAGES', '0') == '1' and hprev_split_wanted(T, B, H, ndir)
+    at the price the separate pass pays at HBM speed.  Not the default.  hprev: as in fwd_ysplit_wanted."""
+    return (os.environ.get('XPS_FWD_IMAGES', '0') == '1' and (hprev_split_wanted(T, B, H, ndir) if hprev is None else hprev)
             and bool(lib().xps_gru_seq_fwd_images_supported(T, B, H, ndir)))
 
 
@@ -444,7 +437,8 @@ def _gru_forward_images(gi, w_hh, b_hh, T, B, H, ndir, save, want_dropped, drop)
     y_split = torch.empty(T + 2, B, ndir * H, dtype=_f32, device=dev) if save else None
     yd_split = torch.empty(T, B, ndir * H, dtype=_f32, device=dev) if want_dropped else None
     saved = torch.empty(ndir, T, B, 4 * H, dtype=_f32, device=dev) if save else None
-    _stamp_saved(saved, B, H)
+    if save:
+        saved.launch_form = _launch_form(B, H)
     nbytes = _gru_ws_bytes('xps_gru_seq_fwd_f32_workspace', T, B, H, ndir)
     ws = _ws(nbytes, dev)
     _gru_status_register(dev)
@@ -462,12 +456,13 @@ def gru_forward_training_form(gi, w_hh, b_hh, T, B, H, ndir):
     return _gru_forward(gi, w_hh, b_hh, None, T, B, H, ndir, True)
 
 
-def _gru_backward(dy, dhn, y_ext, saved, w_hh, T, B, H, ndir, need_dh0, drop=None, split4=False):
+def _gru_backward(dy, dhn, y_ext, saved, w_hh, T, B, H, ndir, need_dh0, drop=None, split4=False, form=None):
     """BPTT kernel.  dy (T,B,ndir*H) or None, dhn (ndir,B,H) or None.  Returns dgi (ndir,T,B,3H),
     dghn (ndir,T,B,H), dh0 (ndir,B,H) or None.  split4 (only where split4_supported): dgi / dghn hold XPS_FMT_SPLIT4
-    groups -- GEMM operands to be described with rowmap(..., fmt=1), not fp32 values."""
+    groups -- GEMM operands to be described with rowmap(..., fmt=1), not fp32 values.  form: the _launch_form of the forward
+    that wrote `saved` (default: what _gru_forward left on `saved`, if anything)."""
     dev = y_ext.device
-    _check_saved(saved, B, H)
+    _check_form(form if form is not None else getattr(saved, 'launch_form', None), B, H)
     if dy is not None and not dy.is_contiguous():
         dy = dy.contiguous()
     if dhn is not None and not dhn.is_contiguous():
@@ -510,12 +505,7 @@ def _recurrent_grad_problems(dgi, dghn, y_ext, w_hh_params, b_hh_params, T, B, H
     ldy = ndir * H
     probs, rets = [], []
     for d in range(ndir):
-        dw, acc_w, rw = _grad_target(w_hh_params[d], (3 * H, H), dev)
-        db, acc_b, rb = _grad_target(b_hh_params[d], (3 * H,), dev)
-        if acc_w != acc_b:
-            dw, acc_w = torch.empty(3 * H, H, dtype=_f32, device=dev), False
-            db, acc_b = torch.empty(3 * H, dtype=_f32, device=dev), False
-            rw, rb = dw, db
+        dw, db, acc_w, rw, rb = _grad_targets(w_hh_params[d], (3 * H, H), b_hh_params[d], (3 * H,), dev)
         first_slot = 0 if d == 0 else 2
         hprev = y_ext.view(-1)[first_slot * B * ldy + d * H:]
         probs.append(tn_problem(dgi[d], hprev, dw, 2 * H, H, T * B, ra=rowmap(3 * H, fmt=fmt), rb=rowmap(ldy, fmt=y_fmt), rc=rowmap(H),
@@ -543,6 +533,7 @@ class GRURecurFn(torch.autograd.Function):
         y_ext, saved = _gru_forward(gi, w_hh, b_hh, h0c, T, B, H, ndir, save)
         if save:
             ctx.save_for_backward(y_ext, saved, *w_hh)
+            ctx.form = saved.launch_form
         ctx.params = wb
         ctx.dims = (T, B, H, ndir)
         ctx.has_h0 = h0 is not None
@@ -553,7 +544,7 @@ class GRURecurFn(torch.autograd.Function):
         y_ext, saved, *w_hh = ctx.saved_tensors
         T, B, H, ndir = ctx.dims
         need_dh0 = ctx.has_h0 and ctx.needs_input_grad[1]
-        dgi, dghn, dh0 = _gru_backward(dy_ext[1:T + 1], None, y_ext, saved, w_hh, T, B, H, ndir, need_dh0)
+        dgi, dghn, dh0 = _gru_backward(dy_ext[1:T + 1], None, y_ext, saved, w_hh, T, B, H, ndir, need_dh0, form=ctx.form)
         if need_dh0:                                   # gradient that arrived directly on the h0 slots of y_ext
             dh0[0] += dy_ext[0, :, :H]
             if ndir == 2:
@@ -614,6 +605,40 @@ def split4(x, drop_p=0.0, seed=0):
     return out
 
 
+class GruPlan(NamedTuple):
+    """Everything that is decided for one GRULayerFmtFn call: made once by gru_layer_plan in the forward, obeyed by the backward."""
+    cluster_on: bool        # launch form of the recurrence (_launch_form)
+    precision: int          # xps_get_gemm_precision() the formats below were chosen under
+    drop_fused: bool        # the recurrence kernels apply the inter-layer dropout (else: a separate pass each way)
+    x_fmt: int              # x holds XPS_FMT_SPLIT4 groups (FMT_X_SPLIT4)
+    w_fmt: int              # W_ih is split once per forward pass (_presplit_weights_ok)
+    y_out_split: bool       # the dropped output is written as XPS_FMT_SPLIT4 groups (FMT_Y_SPLIT4)
+    fwd_images: bool        # fwd_images_wanted
+    fwd_ysplit: bool        # fwd_ysplit_wanted
+    want_dropped: bool      # the forward launch also writes the image of the dropped output
+    bwd_split4: int         # dgi / dghn as XPS_FMT_SPLIT4 operands (split4_wanted): they only feed GEMMs, same bits
+    y_fmt: int              # dW_hh reads h_prev from a split4 image of the state sequence (hprev_split_wanted)
+    skinny_dx: bool         # skinny_dx_wanted
+
+
+def gru_layer_plan(T, B, In, H, ndir, drop_p, fmt):
+    """The GruPlan of one layer call under the library state and the environment switches of this moment."""
+    has_drop = bool(drop_p and drop_p > 0.0)
+    drop_fused = bool(has_drop and fused_dropout_supported(T, B, H, ndir))
+    y_out_split = bool(fmt & FMT_Y_SPLIT4)
+    if y_out_split and (not has_drop or drop_fused):
+        raise ValueError('FMT_Y_SPLIT4: only with a separate dropout pass (see layer_output_split4_ok)')
+    w_fmt = 1 if _presplit_weights_ok(T * B, In, 3 * H) else 0
+    split4 = bool(split4_wanted(T, B, H, ndir))
+    hprev = bool(hprev_split_wanted(T, B, H, ndir, split4))
+    fwd_images = bool(fwd_images_wanted(T, B, H, ndir, hprev))
+    return GruPlan(cluster_on=lib().xps_get_gru_cluster_mode() != 0, precision=lib().xps_get_gemm_precision(), drop_fused=drop_fused,
+                   x_fmt=1 if (fmt & FMT_X_SPLIT4) else 0, w_fmt=w_fmt, y_out_split=y_out_split, fwd_images=fwd_images,
+                   fwd_ysplit=bool(fwd_ysplit_wanted(T, B, H, ndir, hprev)), want_dropped=fwd_images and y_out_split,
+                   bwd_split4=int(split4), y_fmt=int(hprev),
+                   skinny_dx=bool(split4 and not w_fmt and skinny_dx_wanted(T * B, In, 3 * H)))
+
+
 class GRULayerFmtFn(torch.autograd.Function):
     """One (bi)directional GRU layer over a time-major input x (T, B, In):
     input projection GEMMs for all steps + fused recurrence; backward = BPTT kernel + ONE grouped
@@ -632,18 +657,17 @@ class GRULayerFmtFn(torch.autograd.Function):
         _need_gpu(x, *wb)
         x = x.contiguous()
         T, B, In = x.shape
-        x_fmt = 1 if (fmt & FMT_X_SPLIT4) else 0
         w_ih = [wb[4 * d + 0].contiguous() for d in range(ndir)]
         w_hh = [wb[4 * d + 1].contiguous() for d in range(ndir)]
         b_ih = [wb[4 * d + 2].contiguous() for d in range(ndir)]
         b_hh = [wb[4 * d + 3].contiguous() for d in range(ndir)]
         H = w_hh[0].shape[1]
+        plan = ctx.plan = gru_layer_plan(T, B, In, H, ndir, drop_p, fmt)
         gi = torch.empty(ndir, T, B, 3 * H, dtype=_f32, device=x.device)
         # large layers: W_ih split once per forward pass (its readers: this projection and the backward's input gradient)
-        w_fmt = 1 if _presplit_weights_ok(T * B, In, 3 * H) else 0
-        if w_fmt:
+        if plan.w_fmt:
             w_ih = [split4(w) for w in w_ih]
-        ra, rb, rc = rowmap(In, fmt=x_fmt), rowmap(In, fmt=w_fmt), rowmap(3 * H)          # all directions in ONE launch
+        ra, rb, rc = rowmap(In, fmt=plan.x_fmt), rowmap(In, fmt=plan.w_fmt), rowmap(3 * H)          # all directions in ONE launch
         call('xps_gemm_nt_multi_f32', _ptr(x), C.byref(ra), _ptr_array(w_ih), C.byref(rb), _ptr_array([gi[d] for d in range(ndir)]),
              C.byref(rc), _ptr_array(b_ih), ndir, T * B, 3 * H, In, _stream())
         save = any(ctx.needs_input_grad)
@@ -652,23 +676,18 @@ class GRULayerFmtFn(torch.autograd.Function):
         if drop_p and drop_p > 0.0:
             drop = (float(drop_p), next_dropout_seed())
         ctx.drop = drop
-        ctx.drop_fused = bool(drop is not None and fused_dropout_supported(T, B, H, ndir))
         y_split = None
-        opt_in = fwd_images_wanted(T, B, H, ndir)
-        want_dropped = opt_in and bool(fmt & FMT_Y_SPLIT4) and drop is not None and not ctx.drop_fused
-        if (save and (opt_in or fwd_ysplit_wanted(T, B, H, ndir))) or want_dropped:
+        if (save and (plan.fwd_images or plan.fwd_ysplit)) or plan.want_dropped:
             # the recurrence kernel's epilogue writes the split4 images of y_ext (h_prev of dW_hh) and of the dropped output
-            y_ext, saved, y_split, y_drop = _gru_forward_images(gi, w_hh, b_hh, T, B, H, ndir, save, want_dropped, drop)
-        elif ctx.drop_fused:
+            y_ext, saved, y_split, y_drop = _gru_forward_images(gi, w_hh, b_hh, T, B, H, ndir, save, plan.want_dropped, drop)
+        elif plan.drop_fused:
             y_ext, saved, y_drop = _gru_forward(gi, w_hh, b_hh, None, T, B, H, ndir, save, drop)
         else:
             y_ext, saved = _gru_forward(gi, w_hh, b_hh, None, T, B, H, ndir, save)
-        ctx.has_y_split = y_split is not None
-        if save:
+        if save:                                # (y_split: there iff plan.fwd_images or plan.fwd_ysplit)
             ctx.save_for_backward(x, y_ext, saved, *w_ih, *w_hh, *([y_split] if y_split is not None else []))
         ctx.params = wb
         ctx.dims = (T, B, H, ndir, In, hn_mode)
-        ctx.fmts = (x_fmt, w_fmt)
         # y: per-step outputs (a view of y_ext: slots 1..T); hn: final hidden state of each direction
         # (forward: t = T-1, reverse: t = 0), returned separately so that a consumer of the final state
         # only (the seq2seq encoder) sends back a small gradient instead of a zero-padded (T, B, .) one
@@ -677,13 +696,11 @@ class GRULayerFmtFn(torch.autograd.Function):
             y = y_drop
         elif drop is not None:                  # shapes without the fused path: the same decisions in a separate pass
             out = torch.empty(T, B, ndir * H, dtype=_f32, device=x.device)
-            if fmt & FMT_Y_SPLIT4:              # same decisions and values, written as the hi / lo split the next layer's GEMMs stage
+            if plan.y_out_split:                # same decisions and values, written as the hi / lo split the next layer's GEMMs stage
                 call('xps_split4_f32', _ptr(y), _ptr(out), out.numel(), drop[0], drop[1], _stream())
             else:
                 call('xps_dropout_f32', _ptr(y), _ptr(out), None, out.numel(), drop[0], drop[1], _stream())
             y = out
-        if (fmt & FMT_Y_SPLIT4) and (drop is None or ctx.drop_fused):
-            raise ValueError('FMT_Y_SPLIT4: only with a separate dropout pass (see layer_output_split4_ok)')
         if hn_mode == HN_NONE:
             hn = None
         elif hn_mode == HN_SUM:
@@ -697,35 +714,34 @@ class GRULayerFmtFn(torch.autograd.Function):
         T, B, H, ndir, In, hn_mode = ctx.dims
         if dhn is not None and hn_mode == HN_SUM:          # the same (B, H) gradient reaches both directions
             dhn = dhn.unsqueeze(0).expand(ndir, B, H).contiguous()
+        plan = ctx.plan
+        if lib().xps_get_gemm_precision() != plan.precision:
+            names = {v: k for k, v in GEMM_PRECISIONS.items()}
+            raise RuntimeError(f'GRU backward: the forward chose its operand formats in {names[plan.precision]} mode but the backward '
+                               f'runs in {names[lib().xps_get_gemm_precision()]} mode: the product precision (set_gemm_precision / '
+                               'XPS_GEMM_PRECISION) must not change between a forward and its backward')
         x, y_ext, saved, *w = ctx.saved_tensors
-        y_split = w.pop() if ctx.has_y_split else None
+        y_split = w.pop() if (plan.fwd_images or plan.fwd_ysplit) else None
         w_ih, w_hh = w[:ndir], w[ndir:]
-        x_fmt, w_fmt = ctx.fmts
+        fmt, y_fmt, x_fmt, w_fmt = plan.bwd_split4, plan.y_fmt, plan.x_fmt, plan.w_fmt
         wb = ctx.params
-        if ctx.drop is not None and dy is not None and not ctx.drop_fused:
+        if ctx.drop is not None and dy is not None and not plan.drop_fused:
             dyc = dy.contiguous()
             dyd = torch.empty_like(dyc)
             call('xps_dropout_f32', _ptr(dyc), _ptr(dyd), None, dyc.numel(), ctx.drop[0], ctx.drop[1], _stream())
             dy = dyd
-        fmt = 1 if split4_wanted(T, B, H, ndir) else 0           # dgi / dghn only feed GEMMs: pre-split operands, same bits
-        dgi, dghn, _ = _gru_backward(dy, dhn, y_ext, saved, w_hh, T, B, H, ndir, False, ctx.drop if ctx.drop_fused else None,
-                                     split4=bool(fmt))
+        dgi, dghn, _ = _gru_backward(dy, dhn, y_ext, saved, w_hh, T, B, H, ndir, False, ctx.drop if plan.drop_fused else None,
+                                     split4=bool(fmt), form=(plan.cluster_on, B, H))
         dev = x.device
         # weight gradients first: on the side stream they depend on the recurrence kernel only, so they start
         # together with the input-gradient GEMM below instead of after it (and are out of the way earlier)
-        y_fmt = 1 if (fmt and hprev_split_wanted(T, B, H, ndir)) else 0
-        have_img = bool(y_fmt and y_split is not None)                 # written by the forward kernel (fwd_images_wanted)
+        have_img = y_split is not None                                 # written by the forward kernel (an image: only where y_fmt)
         y_src = (y_split if have_img else torch.empty_like(y_ext)) if y_fmt else y_ext   # (else filled on the group's stream: below)
         probs, rets_hh = _recurrent_grad_problems(dgi, dghn, y_src, [wb[4 * d + 1] for d in range(ndir)],
                                                   [wb[4 * d + 3] for d in range(ndir)], T, B, H, ndir, fmt, y_fmt)
         rets_ih = []
         for d in range(ndir):
-            dw, acc_w, rw = _grad_target(wb[4 * d + 0], (3 * H, In), dev)
-            db, acc_b, rb = _grad_target(wb[4 * d + 2], (3 * H,), dev)
-            if acc_w != acc_b:
-                dw, acc_w = torch.empty(3 * H, In, dtype=_f32, device=dev), False
-                db = torch.empty(3 * H, dtype=_f32, device=dev)
-                rw, rb = dw, db
+            dw, db, acc_w, rw, rb = _grad_targets(wb[4 * d + 0], (3 * H, In), wb[4 * d + 2], (3 * H,), dev)
             probs.append(tn_problem(dgi[d], x, dw, 3 * H, In, T * B, ra=rowmap(3 * H, fmt=fmt), rb=rowmap(In, fmt=x_fmt),
                                     colsum_out=db, accumulate=acc_w))
             rets_ih.append((rw, rb))
@@ -738,7 +754,7 @@ class GRULayerFmtFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(T, B, In, dtype=_f32, device=dev)
-            if fmt and not w_fmt and skinny_dx_wanted(T * B, In, 3 * H):
+            if plan.skinny_dx:
                 # few input channels (configs[3] layer 0: In = 100): dx = dgi W_ih is bound by the read of dgi (503 MB), not by the
                 # matrix pipe -- W_ih as a zero-padded 256-column split4 image, so that the product takes ONE 256-wide tile per 256
                 # rows on the LDS-DMA loop (gemm_big_kernel<.., 5>) instead of 64-row edge tiles; measured SLOWER (261 vs 213 us): opt-in, see skinny_dx_wanted
@@ -1050,7 +1066,7 @@ class DecoderWideFn(torch.autograd.Function):
         tokens[0].fill_(int(start_token))
         hs = torch.empty(L + 2, B, H, dtype=_f32, device=dev)            # y_ext layout of a T = L sequence: slot s = h_{s-1}
         saved = torch.empty(1, L, B, 4 * H, dtype=_f32, device=dev) if save else None
-        _stamp_saved(saved, B, H)                                         # (L one-step forwards and one T = L backward share it)
+        ctx.form = _launch_form(B, H)                                     # (L one-step forwards and one T = L backward share it)
         gi = torch.empty(B, 3 * H, dtype=_f32, device=dev)
         nbytes = _gru_ws_bytes('xps_gru_seq_fwd_f32_workspace', 1, B, H, 1)
         _gru_status_register(dev)
@@ -1096,7 +1112,7 @@ class DecoderWideFn(torch.autograd.Function):
         # dy[s, b, :] = dlogits[b, s, :] W_fc for all steps at once (rows (s, b) of dlogits at b*L*C + s*C)
         dy = torch.empty(L, B, H, dtype=_f32, device=dev)
         gemm_nn(dlogits, w_fc_c, dy, L * B, H, C, ra=rowmap(L * C, rpg=B, gs=C))
-        dgi, dghn, dh0 = _gru_backward(dy, None, hs, saved, [w_hh_c], L, B, H, 1, True)
+        dgi, dghn, dh0 = _gru_backward(dy, None, hs, saved, [w_hh_c], L, B, H, 1, True, form=ctx.form)
         dtable, r_wh, r_bh, r_wf, r_bf = _decoder_weight_grads(dlogits, dgi[0], dghn[0], hs, tokens, ctx.params, B, H, C, L, ntok)
         return dtable, dh0[0], r_wh, r_bh, r_wf, r_bf, None, None, None, None
 
@@ -1342,13 +1358,10 @@ class WindowLinearFn(torch.autograd.Function):
         B, T, Cc, nw, K, N, stride = ctx.dims
         dev = x.device
         dout = dout.contiguous()
-        dw, acc_w, rw = _grad_target(w, (N, K), dev)
-        db = rb = None
         if b is not None:
-            db, acc_b, rb = _grad_target(b, (N,), dev)
-            if acc_b != acc_w:
-                dw, db = torch.empty(N, K, dtype=_f32, device=dev), torch.empty(N, dtype=_f32, device=dev)
-                acc_w, rw, rb = False, dw, db
+            dw, db, acc_w, rw, rb = _grad_targets(w, (N, K), b, (N,), dev)
+        else:
+            (dw, acc_w, rw), db, rb = _grad_target(w, (N, K), dev), None, None
         # contraction rows in (w, b) order: dout is plain, the window rows of x are groups of B rows per window
         gemm_tn_grouped([tn_problem(dout, x, dw, N, K, nw * B, ra=rowmap(N),
                                     rb=rowmap(T * Cc, rpg=B, gs=stride * Cc), colsum_out=db, accumulate=acc_w)], dev)

@@ -275,6 +275,72 @@ def test_launch_form_change_between_forward_and_backward_is_refused(cluster_mode
     xf.check_gru_status()
 
 
+def test_backward_follows_the_plan_of_its_forward_when_switches_flip_in_between(gemm_precision, monkeypatch):
+    """GRULayerFmtFn.forward decides the operand formats of both passes once (functional.gru_layer_plan) and the backward obeys
+    that plan: a two-layer encoder in training mode whose XPS_SPLIT4 / XPS_HPREV_SPLIT / XPS_FWD_YSPLIT switches go to 0 between
+    forward and backward (memo dropped, so every predicate WOULD answer anew) gives the bits of the run without the flip --
+    outputs, input gradient and every parameter gradient."""
+    from cross_patient_speech_decoding_amd.nn_models.models import EncoderRNN
+    xf = XF()
+    T, B, In, H = 8, 512, 100, 512
+    switches = ('XPS_SPLIT4', 'XPS_HPREV_SPLIT', 'XPS_FWD_YSPLIT')
+    torch.manual_seed(11)
+    enc = EncoderRNN(In, H, 2, dropout=0.3).cuda().train()
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(T, B, In, generator=g).cuda()
+    wy, wl = torch.randn(T, B, 2 * H, generator=g).cuda(), torch.randn(B, H, generator=g).cuda()
+
+    def run(flip):
+        xf._memo.clear()
+        xf._DROP_COUNTER[0] = 12345
+        enc.zero_grad(set_to_none=True)
+        xg = x.clone().requires_grad_(True)
+        y, last = enc.forward_tm_last(xg)
+        loss = (y * wy).sum() + (last * wl).sum()
+        if flip:
+            before = xf.hprev_split_wanted(T, B, H, 2)            # (implies split4_wanted)
+            for k in switches:
+                monkeypatch.setenv(k, '0')
+            xf._memo.clear()
+            assert before == (gemm_precision == 'bf16x3') and not xf.split4_wanted(T, B, H, 2)
+        loss.backward()
+        torch.cuda.synchronize()
+        xf.check_gru_status()
+        return [y.detach().clone(), last.detach().clone(), xg.grad.clone()] + [p.grad.clone() for p in enc.parameters()]
+
+    try:
+        base = run(False)
+        flipped = run(True)
+    finally:
+        monkeypatch.undo()
+        xf._memo.clear()
+    assert len(base) == len(flipped) == 3 + 16
+    for a, b in zip(base, flipped):
+        assert torch.equal(a, b)
+
+
+def test_precision_change_between_forward_and_backward_is_refused():
+    """The plan records the product precision its operand formats were chosen under: a backward in the other precision would mix
+    formats (or hand the library a split4 operand in fp32 mode), so GRULayerFmtFn.backward refuses it up front."""
+    xf = XF()
+    T, B, In, H = 3, 64, 32, 64
+    torch.manual_seed(0)
+    ws = [w.cuda().requires_grad_(True) for w in _weights(torch.nn.GRU(In, H), 1)]
+    x = torch.randn(T, B, In, device='cuda')
+    old = lib().xps_get_gemm_precision()
+    try:
+        xf.set_gemm_precision('bf16x3')
+        y, _ = xf.GRULayerFn.apply(x, 1, xf.HN_NONE, *ws)
+        xf.set_gemm_precision('fp32')
+        with pytest.raises(RuntimeError, match='precision .* must not change between a forward and its backward'):
+            y.sum().backward()
+        y, _ = xf.GRULayerFn.apply(x, 1, xf.HN_NONE, *ws)
+        y.sum().backward()                               # same precision: accepted
+        torch.cuda.synchronize()
+    finally:
+        lib().xps_set_gemm_precision(old)
+
+
 def test_cluster_path_is_bounded_by_its_largest_32_bit_buffer():
     """The cluster kernels address y_ext, saved and dgi through raw buffer descriptors (32-bit sizes / offsets).  The shape
     guard must bound the LARGEST of them (saved: ndir * T * B * 4H floats), not y_ext alone: at B = 2048, H = 512, both

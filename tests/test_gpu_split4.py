@@ -284,7 +284,7 @@ def test_encoder_stack_with_split4_tensors_equals_the_fp32_tensor_path(H, In, mo
 
     def run(flag):
         monkeypatch.setenv('XPS_SPLIT4', flag)
-        F._split4_ok.clear()
+        F._memo.clear()
         F._DROP_COUNTER[0] = 12345
         enc.zero_grad(set_to_none=True)
         xg = x.clone().requires_grad_(True)
@@ -296,7 +296,7 @@ def test_encoder_stack_with_split4_tensors_equals_the_fp32_tensor_path(H, In, mo
 
     y0, l0, dx0, g0 = run('0')
     y1, l1, dx1, g1 = run('1')
-    F._split4_ok.clear()
+    F._memo.clear()
     assert torch.equal(y1, y0) and torch.equal(l1, l0) and torch.equal(dx1, dx0)
     for k in g0:
         if 'bias' in k:

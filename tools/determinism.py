@@ -23,8 +23,9 @@ def run(H, B, C, steps=4, drop=0.3):
         out.append((float(loss), g, hashlib.md5(opt.flat_p.cpu().numpy().tobytes()).hexdigest()[:8]))
     return out
 
-for H, B, C in ((64, 150, 48), (128, 2048, 64)):
+for H, B, C in ((64, 150, 48), (128, 2048, 64), (512, 2048, 30)):       # (the last: bench.py's configs3 -- cluster recurrence, split4 operands)
     a = run(H, B, C); b = run(H, B, C)
     print(H, B, 'same-process identical:', a == b)
     for s, (u, v) in enumerate(zip(a, b)):
         print('  step', s, u, v if u != v else '')
+XF.check_gru_status()

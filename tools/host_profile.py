@@ -4,7 +4,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 from cross_patient_speech_decoding_amd.nn_models.trainer import FlatAdamW
-c = bench.CFG
+c = bench.WORKLOADS['configs3']
 torch.manual_seed(1234)
 model = bench.build_model(c).cuda()
 opt = FlatAdamW(model, lr=1e-4, weight_decay=1e-5, max_norm=0.5)
