@@ -120,6 +120,10 @@ SIGNATURES = {
     'xps_cross_entropy_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp]),
     'xps_cross_entropy_loss_grad_f32_workspace': (_sz, [_i64]),
     'xps_cross_entropy_loss_grad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i64, _i, _vp]),
+    'xps_classify_loss_acc_f32_workspace': (_sz, [_i64]),
+    'xps_classify_loss_acc_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i64, _i, _vp]),
+    'xps_time_max_fwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    'xps_time_max_bwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'xps_ctc_loss_f32_workspace': (_sz, [_i, _i, _i]),
     'xps_ctc_loss_f32': (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'xps_sumsq_f32_workspace': (_sz, [_i64]),

@@ -4,6 +4,7 @@
 // clip-by-global-norm + AdamW update over the flat parameter buffer.
 // All reductions are two-stage and deterministic (no float atomics).
 #include "xps_common.h"
+#include "xps_ce.h"
 
 namespace {
 
@@ -891,48 +892,23 @@ extern "C" int xps_cross_entropy_fwd_f32(const float* logits, const int64_t* tar
 // Loss AND unit gradient in ONE launch (the three-kernel form costs two more ~5 us launches plus their host time per
 // step): every block handles 256 rows -- row losses, d(mean loss)/d(logits) = (softmax - onehot) / rows -- and leaves its
 // partial loss sum (double); the block that takes the last ticket adds the partials IN INDEX ORDER (the result does not depend
-// on which block that is) and resets the ticket for the next call.  Partials are published with agent-scope fences around
-// the ticket (cdna_hip_programming.md, Guideline 16): release before the atomic, acquire after it in the last block.
-__global__ __launch_bounds__(256) void ce_loss_grad_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
-                                                           float* __restrict__ row_loss, float* __restrict__ loss,
-                                                           float* __restrict__ dlogits, double* part, unsigned* ticket,
-                                                           long long rows, int C) {
-    __shared__ double sh[256];
+// on which block that is) and resets the ticket for the next call.  The row routine and the reduction live in xps_ce.h: the
+// classification step (xps_classify.hip) shares them.
+__global__ __launch_bounds__(CE_BLOCK) void ce_loss_grad_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                                float* __restrict__ row_loss, float* __restrict__ loss,
+                                                                float* __restrict__ dlogits, double* part, unsigned* ticket,
+                                                                long long rows, int C) {
+    __shared__ double sh[CE_BLOCK];
     __shared__ unsigned last;
-    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long r = (long long)blockIdx.x * CE_BLOCK + threadIdx.x;
     double l = 0.0;
     if (r < rows) {
-        const float* p = logits + r * C;
-        float mx = p[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c]);
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s += expf(p[c] - mx);
-        const long long tg = target[r];
-        const float rl = (logf(s) + mx) - p[tg];
+        const float rl = ce_row(logits + r * C, target[r], C, rows, dlogits ? dlogits + r * C : nullptr);
         row_loss[r] = rl;
         l = (double)rl;
-        if (dlogits) {
-            const float g = 1.f / (float)rows, inv = 1.f / s;
-            for (int c = 0; c < C; ++c) dlogits[r * C + c] = g * (expf(p[c] - mx) * inv - (c == tg ? 1.f : 0.f));
-        }
     }
-    sh[threadIdx.x] = l;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = sh[0];
-        __threadfence();                                          // release: the partial before the ticket
-        last = (atomicAdd(ticket, 1u) == gridDim.x - 1) ? 1u : 0u;
-    }
-    __syncthreads();
-    if (last && threadIdx.x == 0) {
-        __threadfence();                                          // acquire: every block's partial
-        double a = 0.0;
-        for (unsigned b = 0; b < gridDim.x; ++b) a += __hip_atomic_load(part + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        loss[0] = (float)(a / (double)rows);
+    if (ce_block_sum_ticket(l, sh, &last, part, ticket) && threadIdx.x == 0) {
+        loss[0] = ce_mean_of_partials(part, rows);
         __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call on this stream
     }
 }
@@ -949,10 +925,10 @@ extern "C" int xps_cross_entropy_loss_grad_f32(const float* logits, const int64_
         xps_set_error("xps_cross_entropy_loss_grad_f32: workspace too small or misaligned");
         return XPS_E_WORKSPACE;
     }
-    const int blocks = cdiv(rows, 256);
+    const int blocks = cdiv(rows, CE_BLOCK);
     unsigned* ticket = (unsigned*)workspace;              // FIRST word: its place must not depend on the row count (calls of
     double* part = (double*)workspace + 2;                // different sizes share one zero-initialised buffer)
-    hipLaunchKernelGGL(ce_loss_grad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, (const long long*)target,
+    hipLaunchKernelGGL(ce_loss_grad_kernel, dim3(blocks), dim3(CE_BLOCK), 0, (hipStream_t)stream, logits, (const long long*)target,
                        row_loss, loss, dlogits, part, ticket, (long long)rows, n_classes);
     XPS_CHECK_LAUNCH();
     return XPS_OK;

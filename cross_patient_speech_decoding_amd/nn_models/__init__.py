@@ -1,2 +1,2 @@
 from .models import (BaseLightningModel, DecoderRNN, EncoderRNN, Seq2SeqRNN,  # noqa: F401
-                     TemporalConv, cmat_acc)
+                     SimpleGRU, TCN_classifier, TemporalConv, TemporalConvRNN, cmat_acc)

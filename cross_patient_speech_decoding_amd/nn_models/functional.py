@@ -1241,10 +1241,11 @@ def unit_gradient(device):
 _ce_ws = {}
 
 
-def _ce_workspace(rows, device):
-    """Zero-initialised partial-sum / ticket buffer of the fused cross-entropy launch, one per (device, stream): the kernel
-    leaves the ticket at zero, so the buffer is reused by every step."""
-    nbytes = lib().xps_cross_entropy_loss_grad_f32_workspace(rows)
+def _ce_workspace(rows, device, query='xps_cross_entropy_loss_grad_f32_workspace'):
+    """Zero-initialised partial-sum / ticket buffer of the fused cross-entropy launch and of the one-launch classification
+    step (`query`: the size query of the entry point), one per (device, stream): both kernels leave the ticket at zero, so
+    the buffer is reused by every step."""
+    nbytes = getattr(lib(), query)(rows)
     key = (device.index, _stream())
     t = _ce_ws.get(key)
     if t is None or t.numel() < nbytes:
@@ -1283,6 +1284,89 @@ class CrossEntropyFn(torch.autograd.Function):
 
 def cross_entropy(logits, target):
     return CrossEntropyFn.apply(logits, target)
+
+
+class ClassifyLossAccFn(torch.autograd.Function):
+    """The classification step of the single-label models in ONE launch: mean cross-entropy (the bits of CrossEntropyFn) with
+    its gradient, the confusion matrix of argmax(logits) against the target, and accuracy = trace / rows.  Returns
+    (loss, acc, cmat); only loss carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, target, num_classes):
+        _need_gpu(logits, target)
+        logits = logits.contiguous()
+        target = target.contiguous()
+        rows, Cn = logits.shape
+        if Cn != num_classes:
+            raise ValueError(f'classify_loss_acc: logits have {Cn} columns, num_classes = {num_classes}')
+        if target.dtype != torch.int64 or target.shape != (rows,):
+            raise ValueError('classify_loss_acc: target must be an int64 vector with one class per row')
+        dev = logits.device
+        row_loss = torch.empty(rows, dtype=_f32, device=dev)
+        loss = torch.empty(1, dtype=_f32, device=dev)
+        acc = torch.empty(1, dtype=_f32, device=dev)
+        cmat = torch.empty(Cn, Cn, dtype=torch.int64, device=dev)        # zeroed by the kernel
+        dl = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        ws, _ = _ce_workspace(rows, dev, 'xps_classify_loss_acc_f32_workspace')
+        call('xps_classify_loss_acc_f32', _ptr(logits), _ptr(target), _ptr(row_loss), _ptr(loss), _ptr(dl), _ptr(cmat), _ptr(acc),
+             _ptr(ws), ws.numel(), rows, Cn, _stream())
+        ctx.unit = dl
+        acc = acc.view(())
+        ctx.mark_non_differentiable(acc, cmat)
+        return loss.view(()), acc, cmat
+
+    @staticmethod
+    def backward(ctx, gout, _gacc, _gcmat):
+        dl = ctx.unit
+        key = (gout.device.type, gout.device.index)
+        one = _unit_grads.get(key)
+        if one is not None and gout.data_ptr() == one.data_ptr():
+            return dl, None, None                        # d loss / d loss = the resident 1.0: nothing to scale
+        return dl * gout.to(_f32), None, None
+
+
+def classify_loss_acc(logits, target, num_classes):
+    """(loss, acc, cmat) of (rows, num_classes) logits against int64 targets (rows,), one launch (ClassifyLossAccFn)."""
+    return ClassifyLossAccFn.apply(logits, target, num_classes)
+
+
+class TimeMaxFn(torch.autograd.Function):
+    """Max over time of a time-major (T, B, F) tensor -> (B, F); torch.max(z, dim=0)'s values under its CPU tie / NaN rule
+    (first maximum wins, a NaN counts as the maximum), and the int32 time index of each.  The saved index routes the gradient: the backward writes
+    every element of dz once (no memset, no atomics)."""
+
+    @staticmethod
+    def forward(ctx, z):
+        _need_gpu(z)
+        if z.dim() != 3 or z.dtype != _f32:
+            raise ValueError('time_max: expected a float32 (T, B, F) tensor')
+        z = z.contiguous()
+        T, B, F = z.shape
+        if T < 1 or B < 1 or F < 1:
+            raise ValueError('time_max: empty tensor')
+        out = torch.empty(B, F, dtype=_f32, device=z.device)
+        arg = torch.empty(B, F, dtype=torch.int32, device=z.device)
+        call('xps_time_max_fwd_f32', _ptr(z), _ptr(out), _ptr(arg), T, B, F, _stream())
+        ctx.save_for_backward(arg)
+        ctx.T = T
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        arg, = ctx.saved_tensors
+        B, F = arg.shape
+        dout = dout.contiguous()
+        dz = torch.empty(ctx.T, B, F, dtype=_f32, device=dout.device)
+        call('xps_time_max_bwd_f32', _ptr(dout), _ptr(arg), _ptr(dz), ctx.T, B, F, _stream())
+        return dz
+
+
+def time_max(z, return_indices=False):
+    """max over the time axis of a time-major (T, B, F) tensor -> (B, F) (TimeMaxFn); return_indices: also the int32 time
+    index of each maximum."""
+    out, arg = TimeMaxFn.apply(z)
+    return (out, arg) if return_indices else out
 
 
 class CTCLossFn(torch.autograd.Function):

@@ -315,3 +315,148 @@ class Seq2SeqRNN(BaseLightningModel):
         lr_sch = torch.optim.lr_scheduler.LinearLR(optim, start_factor=1.0, end_factor=0.01,
                                                    total_iters=self.decay_iters)
         return {'optimizer': optim, 'lr_scheduler': {'scheduler': lr_sch, 'interval': 'epoch', 'frequency': 1}}
+
+
+# --------------------------------------------------------------------------- #
+# Single-label classifiers (reference :111-205 TemporalConvRNN, :393-448       #
+# TCN_classifier, :764-796 SimpleGRU): one class per trial, y of shape (B,)     #
+# --------------------------------------------------------------------------- #
+def _plain_hip_criterion(criterion):
+    """The default criterion in its plain configuration: the one the fused classification step computes."""
+    return (type(criterion) is _HipCrossEntropyLoss and criterion.weight is None and criterion.reduction == 'mean'
+            and criterion.ignore_index == -100 and criterion.label_smoothing == 0.0)
+
+
+class _ClassifyStepMixin:
+    """training / validation / test step of the single-label classifiers on an (x, y) batch, y (B,) int64: the reference's
+    BaseLightningModel steps (:34-86), logging ``{stage}_loss`` and ``{stage}_acc``.  With the default criterion, loss (+ its
+    gradient), confusion matrix and accuracy come from ONE launch (XF.classify_loss_acc); any other criterion takes the
+    reference's route, ``criterion(y_hat, y)`` plus ``cmat_acc``.  ``predict_step`` is BaseLightningModel's."""
+
+    def _classify_step(self, batch, stage):
+        x, y = batch
+        y_hat = self(x)
+        if _plain_hip_criterion(self.criterion) and y_hat.is_cuda and y_hat.dim() == 2:
+            loss, acc, _ = XF.classify_loss_acc(y_hat, y, self.num_classes)
+        else:
+            loss = self.criterion(y_hat, y)
+            acc = cmat_acc(y_hat, y, self.num_classes)
+        self.log_dict({f'{stage}_loss': loss, f'{stage}_acc': acc}, prog_bar=True)
+        return loss
+
+    def training_step(self, batch, batch_idx):
+        return self._classify_step(batch, 'train')
+
+    def validation_step(self, batch, batch_idx):
+        return self._classify_step(batch, 'val')
+
+    def test_step(self, batch, batch_idx):
+        return self._classify_step(batch, 'test')
+
+
+def _fc_stack(dim_fc, num_classes):
+    """The reference's head for a list ``dim_fc``: Linear(d0, d1), ..., Linear(d_last, num_classes), no activation between."""
+    return nn.Sequential(*[nn.Linear(dim_fc[i], dim_fc[i + 1]) for i in range(len(dim_fc) - 1)]
+                         + [nn.Linear(dim_fc[-1], num_classes)])
+
+
+def _apply_fc(fc, x):
+    """``fc`` (None, nn.Linear or nn.Sequential of nn.Linear: parameter containers) as plain XF.linear calls."""
+    if fc is None:
+        return x
+    for lin in (fc if isinstance(fc, nn.Sequential) else [fc]):
+        x = XF.linear(x, lin.weight, lin.bias)
+    return x
+
+
+class SimpleGRU(nn.Module):
+    """Unidirectional multi-layer GRU -> Linear on the last time step (reference :764-796).  ``gru`` and ``fc`` are parameter
+    containers with the reference's names.  The last step's output of a unidirectional GRU is the last layer's final state:
+    only that state feeds ``fc``, the last layer's per-step output is dropped and its backward gets no (T, B, H) gradient.
+
+    ``bidir=True`` raises NotImplementedError: the reference's own ``Linear(hidden_size, .)`` fails on the 2H-wide output of a
+    bidirectional GRU at the first forward, so there is no behaviour to reproduce."""
+
+    def __init__(self, input_size, hidden_size, out_size, num_layers, dropout=0.3, bidir=False):
+        super().__init__()
+        if bidir:
+            raise NotImplementedError('SimpleGRU(bidir=True): the reference module cannot run it either (its Linear takes '
+                                      'hidden_size inputs, a bidirectional GRU emits 2 * hidden_size)')
+        self.gru = nn.GRU(input_size, hidden_size, num_layers, batch_first=True, bidirectional=False, dropout=dropout)
+        self.fc = nn.Linear(hidden_size, out_size)
+
+    def forward_tm(self, z):
+        """z: (T, B, In) time-major -> (B, out_size)."""
+        rnn = self.gru
+        L = rnn.num_layers
+        y, hn = z, None
+        for l in range(L):
+            # inter-layer dropout travels with the layer (EncoderRNN.forward_tm_last); plain fp32 operands between layers
+            p_drop = float(rnn.dropout) if (l < L - 1 and self.training) else 0.0
+            y, hn = XF.GRULayerFmtFn.apply(y, 1, XF.HN_SUM if l == L - 1 else XF.HN_NONE, p_drop, 0,
+                                           *_gru_layer_weights(rnn, l, 1))
+        return XF.linear(hn, self.fc.weight, self.fc.bias)        # hn = h(T - 1) of the last layer = x[:, -1, :]
+
+    def forward(self, x):
+        """x: (B, T, In) -> (B, out_size)."""
+        return self.forward_tm(x.permute(1, 0, 2))
+
+
+class TemporalConvRNN(_ClassifyStepMixin, BaseLightningModel):
+    """TemporalConv -> SimpleGRU -> optional Linear head, one class per trial (reference :111-205).  Positional constructor
+    order, the three ``dim_fc`` branches (None: the GRU's Linear emits the classes; list: Linear stack; int: one Linear) and the
+    ``state_dict`` keys (``temporal_conv.*``, ``rnn.gru.*``, ``rnn.fc.*``, ``fc.*``) are the reference's."""
+
+    def __init__(self, in_channels, n_filters, num_classes, hidden_size, n_layers, kernel_size, dim_fc=None, stride=1,
+                 padding=0, cnn_dropout=0.3, rnn_dropout=0.3, learning_rate=1e-3, l2_reg=1e-5, criterion=None,
+                 activation=True, decay_iters=20):
+        super().__init__(learning_rate=learning_rate, l2_reg=l2_reg, criterion=criterion)
+        self.num_classes = num_classes
+        self.decay_iters = decay_iters
+        self.temporal_conv = TemporalConv(in_channels, n_filters, kernel_size, stride, padding, cnn_dropout,
+                                          activation=activation)
+        if dim_fc is None:
+            self.rnn = SimpleGRU(n_filters, hidden_size, num_classes, n_layers, dropout=rnn_dropout)
+            self.fc = None
+        elif isinstance(dim_fc, list):
+            self.rnn = SimpleGRU(n_filters, hidden_size, dim_fc[0], n_layers, dropout=rnn_dropout)
+            self.fc = _fc_stack(dim_fc, num_classes)
+        else:
+            self.rnn = SimpleGRU(n_filters, hidden_size, dim_fc, n_layers, dropout=rnn_dropout)
+            self.fc = nn.Linear(dim_fc, num_classes)
+
+    def forward(self, x):
+        """x (B, T, C) -> logits (B, num_classes)."""
+        z = self.temporal_conv.forward_tm(x)                       # (T', B, F)
+        return _apply_fc(self.fc, self.rnn.forward_tm(z))
+
+    def configure_optimizers(self):
+        """AdamW + LinearLR(1.0 -> 0.01 over decay_iters epochs), reference :182-205."""
+        optim = torch.optim.AdamW(self.parameters(), lr=self.learning_rate, weight_decay=self.l2_reg)
+        lr_sch = torch.optim.lr_scheduler.LinearLR(optim, start_factor=1.0, end_factor=0.01,
+                                                   total_iters=self.decay_iters)
+        return {'optimizer': optim, 'lr_scheduler': {'scheduler': lr_sch, 'interval': 'epoch', 'frequency': 1}}
+
+
+class TCN_classifier(_ClassifyStepMixin, BaseLightningModel):
+    """TemporalConv -> max over time -> Linear head, one class per trial (reference :393-448).  The convolution has
+    ``dim_fc[0]`` filters.  A list ``dim_fc`` behaves as in the reference.  An int ``dim_fc`` raises TypeError in the
+    reference (it evaluates ``dim_fc[0]`` first); here it is accepted as ``[dim_fc]`` with ``fc = nn.Linear(dim_fc,
+    num_classes)``, the reference's own else-branch.  The optimiser is BaseLightningModel's plain AdamW, as in the reference."""
+
+    def __init__(self, in_channels, num_classes, dim_fc, kernel_size, stride=1, padding=0, dropout=0.3,
+                 learning_rate=1e-3, l2_reg=1e-5, criterion=None, activation=True):
+        super().__init__(learning_rate=learning_rate, l2_reg=l2_reg, criterion=criterion)
+        self.num_classes = num_classes
+        n_filters = dim_fc[0] if isinstance(dim_fc, list) else dim_fc
+        self.temporal_conv = TemporalConv(in_channels, n_filters, kernel_size, stride, padding, dropout,
+                                          activation=activation)
+        if isinstance(dim_fc, list):
+            self.fc = _fc_stack(dim_fc, num_classes)
+        else:
+            self.fc = nn.Linear(dim_fc, num_classes)
+
+    def forward(self, x):
+        """x (B, T, C) -> logits (B, num_classes)."""
+        z = self.temporal_conv.forward_tm(x)                       # (T', B, F)
+        return _apply_fc(self.fc, XF.time_max(z))                  # max over time: (B, F)

@@ -395,6 +395,24 @@ size_t xps_cross_entropy_loss_grad_f32_workspace(int64_t rows);
 int xps_cross_entropy_loss_grad_f32(const float* logits, const int64_t* target, float* row_loss, float* loss,
                                     float* dlogits, void* workspace, size_t workspace_bytes, int64_t rows,
                                     int n_classes, void* stream);
+/* The classification step of the single-label classifiers (nn_models/models.py:34-86 of the reference: criterion + cmat_acc)
+ * in ONE launch: loss / row_loss / dlogits exactly as xps_cross_entropy_loss_grad_f32 (same row routine, same fixed-order
+ * reduction: bit-identical; dlogits may be NULL: evaluation, no gradient is written); cmat [n_classes][n_classes] int64 =
+ * confusion matrix, rows the true class, columns argmax(logits) (first maximum wins, a NaN counts as the maximum), zeroed and
+ * filled by the launch itself; acc[0] = trace(cmat) / rows as fp32.  Targets outside [0, n_classes) are not counted in cmat.
+ * `workspace` as for xps_cross_entropy_loss_grad_f32, same size and layout (ticket in its first word, zero at the first call,
+ * left zero; one zero-initialised buffer may serve both entry points).                                                    */
+size_t xps_classify_loss_acc_f32_workspace(int64_t rows);
+int xps_classify_loss_acc_f32(const float* logits, const int64_t* target, float* row_loss, float* loss, float* dlogits,
+                              int64_t* cmat, float* acc, void* workspace, size_t workspace_bytes, int64_t rows,
+                              int n_classes, void* stream);
+/* Max over time of a TIME-major tensor z [T][B][F] (TCN_classifier, nn_models/models.py:444 of the reference: torch.max over
+ * the time axis): out [B][F] = the maximum, arg [B][F] int32 = its time index.  Among equal maxima the first index wins; a
+ * NaN counts as the maximum and the first NaN wins (torch.max on the CPU).  out is a selection: bit-exact.
+ * 16-byte accesses where F % 4 == 0 and the pointers are 16-byte aligned, 4-byte accesses otherwise.                        */
+int xps_time_max_fwd_f32(const float* z, float* out, int* arg, int T, int B, int F, void* stream);
+/* dz [T][B][F]: dz[t][b][f] = dout[b][f] where t == arg[b][f], else 0.  EVERY element of dz is written (no memset needed). */
+int xps_time_max_bwd_f32(const float* dout, const int* arg, float* dz, int T, int B, int F, void* stream);
 /* CTC loss of the realtime CTC-RNN family (realtime_sim/realtime_nn_model.py:150, :213-224:
  * nn.CTCLoss(blank, reduction='mean', zero_infinity) on log_softmax(logits)).  logits [T][B][C] TIME-major raw
  * scores (the log-softmax is fused); targets [B][target_stride] int64 (padded); lengths int64 [B].
