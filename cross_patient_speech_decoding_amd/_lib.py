@@ -124,6 +124,18 @@ SIGNATURES = {
     'xps_classify_loss_acc_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i64, _i, _vp]),
     'xps_time_max_fwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'xps_time_max_bwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    'xps_attention_supported': (_i, [_i, _i, _i, _i]),
+    'xps_attention_fwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _vp]),
+    'xps_attention_bwd_f32_workspace': (_sz, [_i, _i, _i, _i]),
+    'xps_attention_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _vp, _sz, _vp]),
+    'xps_add_layer_norm_fwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _f, C.c_uint64, _vp]),
+    'xps_add_layer_norm_bwd_f32_workspace': (_sz, [_i64, _i]),
+    'xps_add_layer_norm_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, C.c_uint64, _vp, _sz, _vp]),
+    'xps_relu_dropout_fwd_f32': (_i, [_vp, _vp, _i64, _f, C.c_uint64, _vp]),
+    'xps_relu_dropout_bwd_f32': (_i, [_vp, _vp, _vp, _i64, _f, _vp]),
+    'xps_add_positional_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'xps_time_mean_fwd_f32': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'xps_time_mean_bwd_f32': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'xps_ctc_loss_f32_workspace': (_sz, [_i, _i, _i]),
     'xps_ctc_loss_f32': (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'xps_sumsq_f32_workspace': (_sz, [_i64]),

@@ -1,2 +1,3 @@
-from .models import (BaseLightningModel, DecoderRNN, EncoderRNN, Seq2SeqRNN,  # noqa: F401
-                     SimpleGRU, TCN_classifier, TemporalConv, TemporalConvRNN, cmat_acc)
+from .models import (BaseLightningModel, CNNTransformer, CosineWarmupScheduler, DecoderRNN, EncoderRNN,  # noqa: F401
+                     PositionalEncoding, Seq2SeqRNN, SimpleGRU, TCN_classifier, TemporalConv, TemporalConvRNN, Transformer,
+                     cmat_acc)

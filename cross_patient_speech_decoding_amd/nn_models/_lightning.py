@@ -33,3 +33,7 @@ except ImportError:
 
         def save_hyperparameters(self, *args, **kwargs):
             pass
+
+        def optimizer_step(self, epoch, batch_idx, optimizer, optimizer_closure=None):
+            """Lightning's hook: one optimiser step.  trainer.Trainer calls it where a model overrides it."""
+            optimizer.step()

@@ -1453,6 +1453,205 @@ class WindowLinearFn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- #
+# Transformer encoder layer                                    #
+# --------------------------------------------------------------------------- #
+ATTENTION_MAX_HEAD_DIM = 128
+LAYER_NORM_MAX_WIDTH = 1024
+
+
+def check_attention_shape(d_model, n_head):
+    """ValueError outside the envelope of the attention kernels: n_head must divide d_model, head dimension <= 128."""
+    if n_head < 1 or d_model < 1 or d_model % n_head != 0:
+        raise ValueError(f'self_attention: n_head = {n_head} does not divide d_model = {d_model}')
+    if d_model // n_head > ATTENTION_MAX_HEAD_DIM:
+        raise ValueError(f'self_attention: head dimension {d_model // n_head} > {ATTENTION_MAX_HEAD_DIM} is outside the kernels\' '
+                         'envelope (there is no fallback)')
+
+
+class SelfAttentionFn(torch.autograd.Function):
+    """Fused multi-head self-attention on the packed in-projection output, time-major rows (xps_attention_fwd_f32 / _bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, qkv, B, S, n_head, p, seed):
+        _need_gpu(qkv)
+        if qkv.dtype != _f32 or qkv.numel() == 0 or qkv.shape[-1] % 3 != 0:
+            raise ValueError('self_attention: expected a float32 (S * B, 3 * d_model) tensor')
+        D = qkv.shape[-1] // 3
+        check_attention_shape(D, n_head)
+        if B < 1 or S < 1 or qkv.numel() != S * B * 3 * D:
+            raise ValueError(f'self_attention: {tuple(qkv.shape)} is not S * B = {S} * {B} rows of 3 * d_model')
+        dh = D // n_head
+        if not lib().xps_attention_supported(B, S, n_head, dh):
+            raise ValueError(f'self_attention: shape B = {B}, S = {S}, heads = {n_head}, head dimension = {dh} is outside the '
+                             'kernels\' envelope (there is no fallback)')
+        qkv = qkv.contiguous()
+        out = torch.empty(*qkv.shape[:-1], D, dtype=_f32, device=qkv.device)
+        lse = torch.empty(B, n_head, S, dtype=_f32, device=qkv.device)
+        call('xps_attention_fwd_f32', _ptr(qkv), _ptr(out), _ptr(lse), B, S, n_head, dh, float(p), int(seed), _stream())
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.cfg = (B, S, n_head, dh, float(p), int(seed))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        B, S, n_head, dh, p, seed = ctx.cfg
+        dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        nbytes = _memo(('attn_bwd_ws', B, S, n_head, dh), lambda: lib().xps_attention_bwd_f32_workspace(B, S, n_head, dh))
+        ws = _ws(nbytes, qkv.device)
+        call('xps_attention_bwd_f32', _ptr(dout), _ptr(qkv), _ptr(out), _ptr(lse), _ptr(dqkv), B, S, n_head, dh, p, seed, _ptr(ws),
+             nbytes, _stream())
+        return dqkv, None, None, None, None, None
+
+
+def self_attention(qkv, B, S, n_head, p=0.0, training=False):
+    """Multi-head self-attention of S * B time-major rows (row s * B + b) of packed q | k | v, each d_model wide with head h at
+    columns h * dh: softmax((q / sqrt(dh)) k^T) v per (trial, head), heads concatenated -> (S * B, d_model).  Dropout with
+    rate p acts on the probabilities when training (one seed from next_dropout_seed, decision index
+    ((b * n_head + head) * S + query) * S + key).  No attention or key-padding masks."""
+    drop = bool(training and p > 0.0)
+    return SelfAttentionFn.apply(qkv, int(B), int(S), int(n_head), float(p) if drop else 0.0, next_dropout_seed() if drop else 0)
+
+
+class AddLayerNormFn(torch.autograd.Function):
+    """y = LayerNorm(x + dropout(r)) * weight + bias (xps_add_layer_norm_fwd_f32 / _bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, r, weight, bias, eps, p, seed):
+        _need_gpu(x, r, weight, bias)
+        if x.shape != r.shape or x.dtype != _f32 or r.dtype != _f32:
+            raise ValueError('add_layer_norm: x and r must be float32 tensors of one shape')
+        D = x.shape[-1]
+        if D < 1 or D > LAYER_NORM_MAX_WIDTH or x.numel() == 0:
+            raise ValueError(f'add_layer_norm: width {D} is outside the kernel\'s envelope (1 .. {LAYER_NORM_MAX_WIDTH}; there is no '
+                             'fallback)')
+        if tuple(weight.shape) != (D,) or tuple(bias.shape) != (D,):
+            raise ValueError('add_layer_norm: weight and bias must have the width of x')
+        x, r = x.contiguous(), r.contiguous()
+        w, bs = weight.contiguous(), bias.contiguous()
+        rows = x.numel() // D
+        y = torch.empty_like(x)
+        mean = torch.empty(rows, dtype=_f32, device=x.device)
+        rstd = torch.empty(rows, dtype=_f32, device=x.device)
+        call('xps_add_layer_norm_fwd_f32', _ptr(x), _ptr(r), _ptr(w), _ptr(bs), _ptr(y), _ptr(mean), _ptr(rstd), rows, D, float(eps),
+             float(p), int(seed), _stream())
+        ctx.save_for_backward(x, r, w, mean, rstd)
+        ctx.cfg = (rows, D, float(p), int(seed))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, r, w, mean, rstd = ctx.saved_tensors
+        rows, D, p, seed = ctx.cfg
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        dr = torch.empty_like(x) if p > 0.0 else dx          # without dropout both branches get the same gradient: one buffer
+        dw = torch.empty(D, dtype=_f32, device=x.device)
+        db = torch.empty(D, dtype=_f32, device=x.device)
+        nbytes = _memo(('add_ln_bwd_ws', rows, D), lambda: lib().xps_add_layer_norm_bwd_f32_workspace(rows, D))
+        ws = _ws(nbytes, x.device)
+        call('xps_add_layer_norm_bwd_f32', _ptr(dy), _ptr(x), _ptr(r), _ptr(w), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dr), _ptr(dw),
+             _ptr(db), rows, D, p, seed, _ptr(ws), nbytes, _stream())
+        return dx, dr, dw, db, None, None, None
+
+
+def add_layer_norm(x, r, weight, bias, eps=1e-5, p=0.0, training=False):
+    """LayerNorm(x + dropout(r)) * weight + bias over the last axis (biased variance, nn.LayerNorm): the residual add, the
+    dropout of the branch r (rate p when training; decision index = flat element index) and the normalisation in one kernel."""
+    drop = bool(training and p > 0.0)
+    return AddLayerNormFn.apply(x, r, weight, bias, float(eps), float(p) if drop else 0.0, next_dropout_seed() if drop else 0)
+
+
+class ReluDropoutFn(torch.autograd.Function):
+    """out = dropout(relu(x)) in one pass; the saved output is the backward's gate (xps_relu_dropout_fwd_f32 / _bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed):
+        _need_gpu(x)
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        call('xps_relu_dropout_fwd_f32', _ptr(x), _ptr(out), x.numel(), float(p), int(seed), _stream())
+        ctx.save_for_backward(out)
+        ctx.p = float(p)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        out, = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = torch.empty_like(out)
+        call('xps_relu_dropout_bwd_f32', _ptr(dout), _ptr(out), _ptr(dx), out.numel(), ctx.p, _stream())
+        return dx, None, None
+
+
+def relu_dropout(x, p=0.0, training=False):
+    """dropout(relu(x)) (the feed-forward block of the encoder layer), one seed from next_dropout_seed when training with p > 0."""
+    drop = bool(training and p > 0.0)
+    return ReluDropoutFn.apply(x, float(p) if drop else 0.0, next_dropout_seed() if drop else 0)
+
+
+class AddPositionalFn(torch.autograd.Function):
+    """z + table[s] written TIME-major (S, B, D); z is (S, B, D), or (B, S, D) with batch_major.  Backward: the identity."""
+
+    @staticmethod
+    def forward(ctx, z, table, batch_major):
+        _need_gpu(z, table)
+        if z.dim() != 3 or z.dtype != _f32 or z.numel() == 0:
+            raise ValueError('add_positional: expected a non-empty float32 3-D tensor')
+        B, S, D = (z.shape[0], z.shape[1], z.shape[2]) if batch_major else (z.shape[1], z.shape[0], z.shape[2])
+        table = table.reshape(-1, table.shape[-1])
+        if table.shape[1] != D or table.shape[0] < S or table.dtype != _f32:
+            raise ValueError(f'add_positional: table {tuple(table.shape)} does not cover {S} steps of width {D}')
+        z, table = z.contiguous(), table.contiguous()
+        out = torch.empty(S, B, D, dtype=_f32, device=z.device)
+        call('xps_add_positional_f32', _ptr(z), _ptr(table), _ptr(out), S, B, D, int(bool(batch_major)), _stream())
+        ctx.batch_major = bool(batch_major)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        return (dout.permute(1, 0, 2) if ctx.batch_major else dout), None, None
+
+
+def add_positional(z, table, batch_major=False):
+    """Time-major (S, B, D) sum of z and the first S rows of the (>= S, D) positional table (a leading axis of 1 is accepted);
+    z is time-major (S, B, D), or batch-major (B, S, D) with batch_major=True (the transposition rides on the add)."""
+    return AddPositionalFn.apply(z, table, batch_major)
+
+
+class TimeMeanFn(torch.autograd.Function):
+    """Mean over time of a time-major (T, B, F) tensor -> (B, F); the sibling of TimeMaxFn."""
+
+    @staticmethod
+    def forward(ctx, z):
+        _need_gpu(z)
+        if z.dim() != 3 or z.dtype != _f32:
+            raise ValueError('time_mean: expected a float32 (T, B, F) tensor')
+        z = z.contiguous()
+        T, B, F = z.shape
+        if T < 1 or B < 1 or F < 1:
+            raise ValueError('time_mean: empty tensor')
+        out = torch.empty(B, F, dtype=_f32, device=z.device)
+        call('xps_time_mean_fwd_f32', _ptr(z), _ptr(out), T, B, F, _stream())
+        ctx.T = T
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dout = dout.contiguous()
+        B, F = dout.shape
+        dz = torch.empty(ctx.T, B, F, dtype=_f32, device=dout.device)
+        call('xps_time_mean_bwd_f32', _ptr(dout), _ptr(dz), ctx.T, B, F, _stream())
+        return dz
+
+
+def time_mean(z):
+    """mean over the time axis of a time-major (T, B, F) tensor -> (B, F) (TimeMeanFn)."""
+    return TimeMeanFn.apply(z)
+
+
+# --------------------------------------------------------------------------- #
 # optimiser                                                                    #
 # --------------------------------------------------------------------------- #
 def grad_sumsq(flat_grad, out=None):

@@ -460,3 +460,142 @@ class TCN_classifier(_ClassifyStepMixin, BaseLightningModel):
         """x (B, T, C) -> logits (B, num_classes)."""
         z = self.temporal_conv.forward_tm(x)                       # (T', B, F)
         return _apply_fc(self.fc, XF.time_max(z))                  # max over time: (B, F)
+
+
+# --------------------------------------------------------------------------- #
+# Transformer classifiers (reference :451-504 Transformer, :506-597              #
+# CNNTransformer, :799-832 PositionalEncoding, :834-873 CosineWarmupScheduler)    #
+# --------------------------------------------------------------------------- #
+class PositionalEncoding(nn.Module):
+    """Sinusoidal table added to a (B, T, d_model) input (reference :799-832).  The table is built with the reference's own
+    operations: an odd ``d_model`` is padded to the next even width and the table cut back to ``d_model`` columns.  Buffer
+    ``pos_encoding`` (1, max_len, d_model), as in the reference's ``state_dict``."""
+
+    def __init__(self, d_model, max_len=5000):
+        super().__init__()
+        dim = d_model + (d_model % 2)
+        enc = torch.zeros(max_len, dim)
+        position = torch.arange(0, max_len, dtype=torch.float).unsqueeze(1)
+        div_term = torch.exp(torch.arange(0, dim, 2).float() * (-torch.log(torch.tensor(10000.0)) / dim))
+        enc[:, 0::2] = torch.sin(position * div_term)
+        enc[:, 1::2] = torch.cos(position * div_term)
+        self.register_buffer('pos_encoding', enc.unsqueeze(0)[:, :, :d_model])
+
+    def forward_tm(self, z, batch_major=False):
+        """z time-major (S, B, D) -- or batch-major (B, S, D) with batch_major -- plus the table -> time-major (S, B, D)."""
+        S = z.shape[1] if batch_major else z.shape[0]
+        if S > self.pos_encoding.shape[1]:
+            raise ValueError(f'PositionalEncoding: sequence length {S} exceeds max_len {self.pos_encoding.shape[1]}')
+        return XF.add_positional(z, self.pos_encoding[0], batch_major)
+
+    def forward(self, x):
+        """x: (B, T, d_model) -> the same shape."""
+        return self.forward_tm(x, batch_major=True).permute(1, 0, 2)
+
+
+class CosineWarmupScheduler(torch.optim.lr_scheduler._LRScheduler):
+    """Linear warm-up over ``warmup`` steps into a cosine decay over ``max_iters`` (reference :834-873)."""
+
+    def __init__(self, optimizer, warmup, max_iters):
+        self.warmup = warmup
+        self.max_num_iters = max_iters
+        super().__init__(optimizer)
+
+    def get_lr(self):
+        lr_factor = self.get_lr_factor(epoch=self.last_epoch)
+        return [base_lr * lr_factor for base_lr in self.base_lrs]
+
+    def get_lr_factor(self, epoch):
+        import numpy as np
+        lr_factor = 0.5 * (1 + np.cos(np.pi * epoch / self.max_num_iters))
+        if epoch <= self.warmup:
+            lr_factor *= epoch * 1.0 / self.warmup
+        return lr_factor
+
+
+def _make_encoder(d_model, n_head, dim_fc, dropout, num_layers):
+    """The reference's nn.TransformerEncoder (its parameter names and initialisation order) as a parameter container."""
+    XF.check_attention_shape(d_model, n_head)
+    layer = nn.TransformerEncoderLayer(d_model, n_head, dim_fc, dropout, batch_first=True)
+    return nn.TransformerEncoder(layer, num_layers, enable_nested_tensor=False)
+
+
+def _encoder_stack_tm(encoder, z, training):
+    """nn.TransformerEncoder (post-norm layers, ReLU, no masks, no final norm) on a time-major (S, B, D) tensor through the HIP
+    kernels.  Per layer: in-projection GEMM, fused attention, out-projection GEMM, add + LayerNorm (dropout1 inside),
+    linear1, ReLU + dropout, linear2, add + LayerNorm (dropout2 inside).  Dropout sites draw their seeds in that order:
+    probabilities, dropout1, feed-forward, dropout2."""
+    S, B, D = z.shape
+    x = z.reshape(S * B, D)
+    for layer in encoder.layers:
+        att = layer.self_attn
+        if layer.norm_first or getattr(layer, 'activation_relu_or_gelu', 1) != 1:
+            raise NotImplementedError('the HIP encoder layer is post-norm with ReLU (the reference\'s configuration)')
+        qkv = XF.linear(x, att.in_proj_weight, att.in_proj_bias)
+        ctx = XF.self_attention(qkv, B, S, att.num_heads, att.dropout, training)
+        a = XF.linear(ctx, att.out_proj.weight, att.out_proj.bias)
+        x = XF.add_layer_norm(x, a, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps, layer.dropout1.p, training)
+        h = XF.relu_dropout(XF.linear(x, layer.linear1.weight, layer.linear1.bias), layer.dropout.p, training)
+        f = XF.linear(h, layer.linear2.weight, layer.linear2.bias)
+        x = XF.add_layer_norm(x, f, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps, layer.dropout2.p, training)
+    if encoder.norm is not None:
+        raise NotImplementedError('a final encoder norm is not part of the reference\'s models')
+    return x.view(S, B, D)
+
+
+class Transformer(_ClassifyStepMixin, BaseLightningModel):
+    """PositionalEncoding -> nn.TransformerEncoder -> mean over time -> Linear, one class per trial (reference :451-504).  The
+    input is (B, T, d_model): ``in_channels`` must equal ``d_model``; ``kernel_size``, ``stride`` and ``padding`` are unused,
+    as in the reference, and kept for its positional constructor order.  ``transformer_encoder`` holds the reference's modules
+    as parameter containers (same ``state_dict``); the arithmetic is _encoder_stack_tm.  Attention masks and key-padding masks
+    are not supported: the reference never passes one.  Raises ValueError where ``n_head`` does not divide ``d_model`` or the
+    head dimension exceeds 128 (the attention kernels' envelope)."""
+
+    def __init__(self, in_channels, num_classes, d_model, kernel_size, stride=1, padding=0, n_head=8, num_layers=3, dim_fc=128,
+                 dropout=0.3, learning_rate=1e-3, l2_reg=1e-5, criterion=None):
+        super().__init__(learning_rate=learning_rate, l2_reg=l2_reg, criterion=criterion)
+        self.num_classes = num_classes
+        self.positional_encoding = PositionalEncoding(d_model)
+        self.transformer_encoder = _make_encoder(d_model, n_head, dim_fc, dropout, num_layers)
+        self.fc = nn.Linear(d_model, num_classes)
+
+    def forward(self, x):
+        """x (B, T, d_model) -> logits (B, num_classes)."""
+        z = self.positional_encoding.forward_tm(x, batch_major=True)              # (T, B, D)
+        z = _encoder_stack_tm(self.transformer_encoder, z, self.training)
+        return XF.linear(XF.time_mean(z), self.fc.weight, self.fc.bias)
+
+
+class CNNTransformer(_ClassifyStepMixin, BaseLightningModel):
+    """TemporalConv -> PositionalEncoding -> nn.TransformerEncoder -> mean over time -> Linear (reference :506-597).
+    Positional constructor order, defaults and ``state_dict`` keys are the reference's.  The optimiser is AdamW with a
+    CosineWarmupScheduler (``warmup``, ``max_epochs``) that ``optimizer_step`` advances after EVERY optimiser step, as in the
+    reference.  No attention or key-padding masks; ValueError outside the attention kernels' envelope (see Transformer)."""
+
+    def __init__(self, in_channels, num_classes, d_model, kernel_size, stride=1, padding=0, n_head=8, num_layers=3, dim_fc=128,
+                 cnn_dropout=0.2, transformer_dropout=0.3, learning_rate=1e-3, warmup=20, max_epochs=500, l2_reg=1e-5,
+                 criterion=None, activation=True):
+        super().__init__(learning_rate=learning_rate, l2_reg=l2_reg, criterion=criterion)
+        self.num_classes = num_classes
+        self.temporal_conv = TemporalConv(in_channels, d_model, kernel_size, stride, padding, cnn_dropout, activation=activation)
+        self.positional_encoding = PositionalEncoding(d_model)
+        self.transformer_encoder = _make_encoder(d_model, n_head, dim_fc, transformer_dropout, num_layers)
+        self.fc = nn.Linear(d_model, num_classes)
+        self.warmup = warmup
+        self.max_epochs = max_epochs
+
+    def forward(self, x):
+        """x (B, T, C) -> logits (B, num_classes)."""
+        z = self.temporal_conv.forward_tm(x)                                      # (T', B, D)
+        z = self.positional_encoding.forward_tm(z)
+        z = _encoder_stack_tm(self.transformer_encoder, z, self.training)
+        return XF.linear(XF.time_mean(z), self.fc.weight, self.fc.bias)
+
+    def configure_optimizers(self):
+        optim = torch.optim.AdamW(self.parameters(), lr=self.learning_rate, weight_decay=self.l2_reg)
+        self.lr_sch = CosineWarmupScheduler(optim, self.warmup, self.max_epochs)
+        return optim
+
+    def optimizer_step(self, *args, **kwargs):
+        super().optimizer_step(*args, **kwargs)
+        self.lr_sch.step()

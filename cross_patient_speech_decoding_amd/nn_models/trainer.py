@@ -243,6 +243,7 @@ class Trainer:
         else:
             opt = cfg
         g = opt.param_groups[0]
+        self._model_optimizer = opt                      # what configure_optimizers returned (a model's own scheduler drives its lr)
         group = self.group
         if group is None and _world()[0] > 1:
             group = dist.group.WORLD                      # one process per GPU: the default group is the data-parallel group
@@ -255,6 +256,19 @@ class Trainer:
                 self.scheduler = LinearLR(self.optimizer, sch.start_factor, sch.end_factor, sch.total_iters)
             else:
                 raise NotImplementedError(f'scheduler {type(sch).__name__} is not supported by the HIP trainer')
+
+    def _optimizer_step(self, model, epoch, batch_idx):
+        """One optimiser step.  A model that overrides Lightning's ``optimizer_step`` hook (CNNTransformer: step, then advance
+        its own scheduler) gets the hook with the flat optimiser; the learning rate its scheduler set on the optimiser that
+        ``configure_optimizers`` returned is carried over.  Every other model: the plain step."""
+        from ._lightning import LightningModule
+        hook = getattr(type(model), 'optimizer_step', None)
+        if hook is None or hook is getattr(LightningModule, 'optimizer_step', None):
+            self.optimizer.step()
+            return
+        self._model_optimizer._opt_called = True         # the flat optimiser steps in its place
+        model.optimizer_step(epoch, batch_idx, self.optimizer)
+        self.optimizer.lr = float(self._model_optimizer.param_groups[0]['lr'])
 
     def _reduce_metrics(self, sums, count):
         world, _ = _world(self.group)
@@ -314,7 +328,7 @@ class Trainer:
                     loss = loss * (x.shape[0] * world / n_global)
                 loss.backward(XF.unit_gradient(loss.device) if loss.dtype == torch.float32 else torch.ones_like(loss))
                 # (resident root gradient: no fill launch per step, and the fused cross-entropy returns its gradient unscaled)
-                self.optimizer.step()
+                self._optimizer_step(model, epoch, bi)
                 n = x.shape[0]
                 for k, v in model._xps_logged.items():
                     sums[k] = sums.get(k, 0.0) + float(v) * n

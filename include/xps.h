@@ -413,6 +413,49 @@ int xps_classify_loss_acc_f32(const float* logits, const int64_t* target, float*
 int xps_time_max_fwd_f32(const float* z, float* out, int* arg, int T, int B, int F, void* stream);
 /* dz [T][B][F]: dz[t][b][f] = dout[b][f] where t == arg[b][f], else 0.  EVERY element of dz is written (no memset needed). */
 int xps_time_max_bwd_f32(const float* dout, const int* arg, float* dz, int T, int B, int F, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Transformer encoder layer (nn_models/models.py:451-597 of the reference:     */
+/* nn.TransformerEncoderLayer, post-norm, ReLU, batch_first) -- DESIGN.md 4.13   */
+/* ------------------------------------------------------------------------- */
+/* Fused multi-head self-attention on TIME-major rows.  qkv [S*B][3 D], D = n_head * dh: row (s, b) = s * B + b holds q | k | v
+ * (the packed in-projection output), head h at columns h * dh of each.  Per (trial b, head h):
+ *   scores = (q / sqrt(dh)) k^T, P = softmax over keys (row maximum subtracted), Pd = P * keep / (1 - p), ctx = Pd v.
+ * ctx [S*B][D] head-concatenated; lse [B][n_head][S] = row maximum + log of the row's sum of exponentials (what the backward
+ * needs to rebuild P).  fp32 throughout; the S x S probabilities exist in registers only; keys stream through LDS in tiles (64
+ * keys, 32 where dh > 64), so S is not bounded by LDS.  keep = the decision xps_dropout_f32(seed) makes for flat index
+ * ((b * n_head + h) * S + query) * S + key  (p = 0: no dropout, seed ignored).  Envelope (xps_attention_supported): B, S,
+ * n_head >= 1, 1 <= dh <= 128. */
+int xps_attention_supported(int B, int S, int n_head, int dh);
+int xps_attention_fwd_f32(const float* qkv, float* ctx, float* lse, int B, int S, int n_head, int dh, float p, uint64_t seed,
+                          void* stream);
+/* dqkv [S*B][3 D] (EVERY element written) from dctx: P is recomputed from q, k and lse, the dropout decisions from the seed.
+ * Two launches: per query (dq, and delta = dctx . ctx into the workspace), then per key (dk, dv: each a sum over the queries in
+ * index order inside one thread).  No atomics: the same bits every run. */
+size_t xps_attention_bwd_f32_workspace(int B, int S, int n_head, int dh);
+int xps_attention_bwd_f32(const float* dctx, const float* qkv, const float* ctx, const float* lse, float* dqkv, int B, int S,
+                          int n_head, int dh, float p, uint64_t seed, void* workspace, size_t workspace_bytes, void* stream);
+/* y = LayerNorm(x + dropout(r)) * gamma + beta over rows of D <= 1024 elements (biased variance, nn.LayerNorm); dropout(r) =
+ * r * keep / (1 - p) with xps_dropout_f32(seed)'s decisions at flat index row * D + column (p = 0: none).  One wave per row; the
+ * row is held in LDS as differences from its first element and the statistics are two passes over it (mean, then the sum of
+ * squared deviations).  mean [rows] (of those differences) and rstd [rows] are what the backward reads. */
+int xps_add_layer_norm_fwd_f32(const float* x, const float* r, const float* gamma, const float* beta, float* y, float* mean,
+                               float* rstd, int64_t rows, int D, float eps, float p, uint64_t seed, void* stream);
+/* dx = d(x + dropout(r)), dr = dx * keep / (1 - p) (p = 0: dr may be the SAME buffer as dx), dgamma / dbeta [D] reduced over the
+ * rows in a fixed order (per wave, per workgroup, then over workgroups in the workspace). */
+size_t xps_add_layer_norm_bwd_f32_workspace(int64_t rows, int D);
+int xps_add_layer_norm_bwd_f32(const float* dy, const float* x, const float* r, const float* gamma, const float* mean,
+                               const float* rstd, float* dx, float* dr, float* dgamma, float* dbeta, int64_t rows, int D, float p,
+                               uint64_t seed, void* workspace, size_t workspace_bytes, void* stream);
+/* out = max(x, 0) * keep / (1 - p), decisions of xps_dropout_f32(seed) at the flat index (the feed-forward block) */
+int xps_relu_dropout_fwd_f32(const float* x, float* out, int64_t n, float p, uint64_t seed, void* stream);
+/* dx = dout / (1 - p) where out > 0 (input positive and kept), else 0: the forward's output is the gate, no seed needed */
+int xps_relu_dropout_bwd_f32(const float* dout, const float* out, float* dx, int64_t n, float p, void* stream);
+/* out [S][B][D] (TIME-major) = z + table[s]; z is [S][B][D], or [B][S][D] where batch_major != 0; table [>= S][D] */
+int xps_add_positional_f32(const float* z, const float* table, float* out, int S, int B, int D, int batch_major, void* stream);
+/* Mean over time of a TIME-major z [T][B][F]: out [B][F] = (z[0] + z[1] + ... in this order) / T; dz[t][b][f] = dout[b][f] / T */
+int xps_time_mean_fwd_f32(const float* z, float* out, int T, int B, int F, void* stream);
+int xps_time_mean_bwd_f32(const float* dout, float* dz, int T, int B, int F, void* stream);
 /* CTC loss of the realtime CTC-RNN family (realtime_sim/realtime_nn_model.py:150, :213-224:
  * nn.CTCLoss(blank, reduction='mean', zero_infinity) on log_softmax(logits)).  logits [T][B][C] TIME-major raw
  * scores (the log-softmax is fused); targets [B][target_stride] int64 (padded); lengths int64 [B].
