@@ -37,6 +37,17 @@ def _ovr_from_ovo(dec, n_classes):
     return votes + sums / (3 * (np.abs(sums) + 1))
 
 
+def _class_weights(class_weight, classes, yi):
+    """sklearn.utils.class_weight.compute_class_weight on the y handed to fit (``yi``: its class indices)."""
+    if class_weight is None:
+        return np.ones(len(classes))
+    if isinstance(class_weight, str):
+        if class_weight != 'balanced':
+            raise ValueError("class_weight must be 'balanced', a dict or None")
+        return len(yi) / (len(classes) * np.bincount(yi, minlength=len(classes)).astype(np.float64))
+    return np.array([float(class_weight.get(c, 1.0)) for c in classes])
+
+
 class SVC(ClassifierMixin, BaseEstimator):
     """C-support vector classification, ``kernel='linear'`` or ``'rbf'`` (sklearn.svm.SVC semantics for these)."""
 
@@ -51,6 +62,15 @@ class SVC(ClassifierMixin, BaseEstimator):
         self.break_ties = break_ties
         self.class_weight = class_weight
         self.random_state = random_state
+
+    def _check_settings(self):
+        """The settings the HIP path does not implement are refused (by ``fit``, and by the bagged ensemble on its estimator)."""
+        if self.kernel not in ('linear', 'rbf'):
+            raise NotImplementedError("the HIP SVC implements kernel='linear' and kernel='rbf' (what the reference's decoders use)")
+        if self.break_ties:
+            raise NotImplementedError('break_ties is not implemented on the HIP path')
+        if self.decision_function_shape not in ('ovr', 'ovo'):
+            raise ValueError("decision_function_shape must be 'ovr' or 'ovo'")
 
     # ------------------------------------------------------------------ kernels
     def _gamma_value(self, X):
@@ -84,27 +104,14 @@ class SVC(ClassifierMixin, BaseEstimator):
 
     # ------------------------------------------------------------------ fit
     def fit(self, X, y, sample_weight=None):
-        if self.kernel not in ('linear', 'rbf'):
-            raise NotImplementedError("the HIP SVC implements kernel='linear' and kernel='rbf' (what the reference's decoders use)")
-        if self.break_ties:
-            raise NotImplementedError('break_ties is not implemented on the HIP path')
-        if self.decision_function_shape not in ('ovr', 'ovo'):
-            raise ValueError("decision_function_shape must be 'ovr' or 'ovo'")
+        self._check_settings()
         X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
         y = np.asarray(y)
         if X.ndim != 2 or X.shape[0] != y.shape[0]:
             raise ValueError('X must be (n_samples, n_features) and y (n_samples,)')
         self._gamma = self._gamma_value(X)
         classes, yi_all = np.unique(y, return_inverse=True)
-        # class weights (sklearn.utils.class_weight.compute_class_weight on the y handed to fit)
-        if self.class_weight is None:
-            cw = np.ones(len(classes))
-        elif isinstance(self.class_weight, str):
-            if self.class_weight != 'balanced':
-                raise ValueError("class_weight must be 'balanced', a dict or None")
-            cw = len(y) / (len(classes) * np.bincount(yi_all, minlength=len(classes)).astype(np.float64))
-        else:
-            cw = np.array([float(self.class_weight.get(c, 1.0)) for c in classes])
+        cw = _class_weights(self.class_weight, classes, yi_all)
         self.class_weight_ = cw
         # sample weights (BaggingClassifier passes the bootstrap multiplicities): per-point bound C * class weight * w; zero-weight
         # points are dropped before training, as sklearn's libsvm does

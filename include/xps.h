@@ -594,6 +594,20 @@ int xps_rbf_from_gram_f64(const double* G, int64_t ldg, const double* na, const 
 size_t xps_svm_smo_f64_max_points(void);
 int xps_svm_smo_f64(const double* K, int64_t ldk, const int* idx, const int* off, const int* npos, int nprob, int max_points,
                     const double* cbound, double eps, int max_iter, double* alpha, double* rho, int* iterations, void* stream);
+/* Bagged SVC ensemble (sklearn's BaggingClassifier(SVC), scripts/aligned_decode_svm.py:262-263): all E x P binary problems of the
+ * ensemble are posed to ONE xps_svm_smo_f64 launch as index lists into one kernel matrix; these two kernels are the rest.
+ * xps_bag_coef_scatter_f64: coef (nprob x n, leading dimension ldc >= n, every element written) = the dense signed dual
+ * coefficients: coef[q][idx[off[q] + t]] = +alpha[off[q] + t] for t < npos[q], -alpha[off[q] + t] for the other points of problem
+ * q, zero elsewhere (idx, off, npos, alpha as in xps_svm_smo_f64; an index outside [0, n) is dropped).
+ * xps_bag_vote_f64: dec is m x Q row-major (ld >= Q), Q = est_off[E]; problem q votes for class pair_a[q] where dec[r][q] - rho[q]
+ * > 0 (strictly) and for pair_b[q] otherwise (pair_a[q] < pair_b[q], indices into the ensemble's classes); estimator e owns the
+ * problems est_off[e] .. est_off[e + 1]) and votes for the class with the most of their votes (ties: the lowest index, libsvm's
+ * rule; an estimator without problems casts no vote); votes[r][c] (m x k, int32) counts the estimators, pred[r] (int32) is the
+ * first maximum of votes[r].  Integer arithmetic, no atomics.  k must be in 2..64: anything else is refused.                    */
+int xps_bag_coef_scatter_f64(const double* alpha, const int* idx, const int* off, const int* npos, int nprob, int n,
+                             double* coef, int64_t ldc, void* stream);
+int xps_bag_vote_f64(const double* dec, int64_t ld, const double* rho, const int* pair_a, const int* pair_b, const int* est_off,
+                     int m, int E, int k, int* votes, int* pred, void* stream);
 /* small dense float64 GEMM  C = op(A) op(B)  (row-major, op = transpose flag) */
 int xps_dgemm_small(const double* A, int64_t lda, int ta, const double* B, int64_t ldb, int tb,
                     double* C, int64_t ldc, int M, int N, int K, void* stream);
