@@ -43,163 +43,68 @@ class XpsError(RuntimeError):
     pass
 
 
-_vp, _i, _i64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
-_rm = C.POINTER(RowMap)
+_CTYPES = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64, 'size_t': C.c_size_t,
+           'float': C.c_float, 'double': C.c_double, 'long long': C.c_longlong}
+_POINTEES = set(_CTYPES) | {'void', 'char', 'unsigned', 'uint8_t', 'xps_rowmap', 'xps_tn_problem'}
 
-# name -> (restype, argtypes); must list every function declared in include/xps.h
-SIGNATURES = {
-    'xps_last_error': (C.c_char_p, []),
-    'xps_abi_version': (_i, []),
-    'xps_stream_create_low_priority': (_i, [_vp]),
-    'xps_stream_destroy': (_i, [_vp]),
-    'xps_set_gemm_precision': (_i, [_i]),
-    'xps_get_gemm_precision': (_i, []),
-    'xps_set_gemm_big_tiles': (_i, [_i]),
-    'xps_get_gemm_big_tiles': (_i, []),
-    'xps_gemm_nt_f32': (_i, [_vp, _rm, _vp, _rm, _vp, _rm, _vp, _i, _i, _i, _i, _vp]),
-    'xps_gemm_nn_f32': (_i, [_vp, _rm, _vp, _rm, _vp, _rm, _i, _i, _i, _i, _vp]),
-    'xps_gemm_nt_multi_f32': (_i, [_vp, _rm, _vp, _rm, _vp, _rm, _vp, _i, _i, _i, _i, _vp]),
-    'xps_gemm_nn2_f32': (_i, [_vp, _vp, _i, _vp, _vp, _i, _rm, _rm, _vp, _rm, _i, _i, _i, _vp]),
-    'xps_gemm_tn_f32_workspace': (_sz, [_i, _i, _i]),
-    'xps_gemm_tn_f32': (_i, [_vp, _rm, _vp, _rm, _vp, _rm, _i, _i, _i, _i, _vp, _sz, _vp]),
-    'xps_gemm_tn_grouped_f32_workspace': (_sz, [_vp, _i]),
-    'xps_gemm_tn_grouped_f32': (_i, [_vp, _i, _vp, _sz, _vp]),
-    'xps_colsum_f32_workspace': (_sz, [_i, _i]),
-    'xps_colsum_f32': (_i, [_vp, _i64, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
-    'xps_gru_seq_fwd_f32_workspace': (_sz, [_i, _i, _i, _i]),
-    'xps_gru_seq_status_offset': (C.c_longlong, [_i, _i, _i, _i]),
-    'xps_gru_set_status_word': (_i, [_vp]),
-    'xps_set_gru_bptt_grid': (_i, [_i]),
-    'xps_get_gru_bptt_grid': (_i, []),
-    'xps_set_gru_cluster_mode': (_i, [_i]),
-    'xps_get_gru_cluster_mode': (_i, []),
-    'xps_gru_seq_fwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
-    'xps_gru_seq_bwd_f32_workspace': (_sz, [_i, _i, _i, _i]),
-    'xps_gru_seq_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
-    'xps_gru_seq_fused_dropout_supported': (_i, [_i, _i, _i, _i]),
-    'xps_gru_seq_fwd_images_supported': (_i, [_i, _i, _i, _i]),
-    'xps_gru_seq_fwd_image_exchange_supported': (_i, [_i, _i, _i, _i]),
-    'xps_gru_seq_fwd_images_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, C.c_uint64, _vp, _sz, _vp]),
-    'xps_gru_seq_fwd_drop_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _f, C.c_uint64, _vp, _sz, _vp]),
-    'xps_gru_seq_bwd_drop_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _vp, _sz, _vp]),
-    'xps_gru_seq_bwd_split4_supported': (_i, [_i, _i, _i, _i]),
-    'xps_gru_seq_bwd_split4_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _vp, _sz, _vp]),
-    'xps_transpose_f32': (_i, [_vp, _vp, _i, _i, _vp]),
-    'xps_transpose_batched_f32': (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    'xps_bn_centered_sumsq_f32': (_i, [_vp, _i, _i, _vp, _d, _vp, _vp, _sz, _vp]),
-    'xps_bn_finalize_f32': (_i, [_vp, _d, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp]),
-    'xps_bn_apply_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i64, _i, _i, _vp]),
-    'xps_bn_finalize_apply_f32': (_i, [_vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _f, _vp, _i64, _i, _i, _vp]),
-    'xps_bn_apply_eval_f32': (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i64, _i, _i, _vp]),
-    'xps_bn_bwd_workspace': (_sz, [_i64, _i]),
-    'xps_bn_bwd_reduce_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _i64, _i, _vp, _sz, _vp]),
-    'xps_bn_bwd_apply_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _d, _vp, _i64, _i, _vp]),
-    'xps_decoder_supported': (_i, [_i, _i, _i]),
-    'xps_decoder_fwd_f32': (_i, [_vp] * 12 + [_i] * 6 + [_vp]),
-    'xps_decoder_bwd_f32': (_i, [_vp] * 8 + [_i] * 4 + [_vp]),
-    'xps_gemv_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    'xps_gru_cell_gemv_f32': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    'xps_gather_rows_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    'xps_scatter_rows_f32_workspace': (_sz, [_i, _i, _i]),
-    'xps_scatter_rows_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
-    'xps_next_token': (_i, [_vp, _i, _vp, _i64, _vp, _vp, _i, _vp]),
-    'xps_window_shift_f32': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    'xps_ctc_collapse_f32': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
-    'xps_ctc_beam_workspace': (_sz, [_i, _i, _i, _i]),
-    'xps_ctc_beam_f64': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    'xps_ctc_beam_state_bytes': (_sz, [_i, _i, _i]),
-    'xps_ctc_beam_step_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
-    'xps_ctc_beam_readout': (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    'xps_decoder_select_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    'xps_dropout_f32': (_i, [_vp, _vp, _vp, _i64, _f, C.c_uint64, _vp]),
-    'xps_split4_f32': (_i, [_vp, _vp, _i64, _f, C.c_uint64, _vp]),
-    'xps_split4_pad_f32': (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp]),
-    'xps_mask_scale_f32': (_i, [_vp, _vp, _f, _vp, _i64, _vp]),
-    'xps_add_f32': (_i, [_vp, _vp, _vp, _i64, _vp]),
-    'xps_cross_entropy_fwd_f32': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp]),
-    'xps_cross_entropy_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp]),
-    'xps_cross_entropy_loss_grad_f32_workspace': (_sz, [_i64]),
-    'xps_cross_entropy_loss_grad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i64, _i, _vp]),
-    'xps_classify_loss_acc_f32_workspace': (_sz, [_i64]),
-    'xps_classify_loss_acc_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i64, _i, _vp]),
-    'xps_time_max_fwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    'xps_time_max_bwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    'xps_attention_supported': (_i, [_i, _i, _i, _i]),
-    'xps_attention_fwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _vp]),
-    'xps_attention_bwd_f32_workspace': (_sz, [_i, _i, _i, _i]),
-    'xps_attention_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_uint64, _vp, _sz, _vp]),
-    'xps_add_layer_norm_fwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _f, C.c_uint64, _vp]),
-    'xps_add_layer_norm_bwd_f32_workspace': (_sz, [_i64, _i]),
-    'xps_add_layer_norm_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, C.c_uint64, _vp, _sz, _vp]),
-    'xps_relu_dropout_fwd_f32': (_i, [_vp, _vp, _i64, _f, C.c_uint64, _vp]),
-    'xps_relu_dropout_bwd_f32': (_i, [_vp, _vp, _vp, _i64, _f, _vp]),
-    'xps_add_positional_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    'xps_time_mean_fwd_f32': (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    'xps_time_mean_bwd_f32': (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    'xps_ctc_loss_f32_workspace': (_sz, [_i, _i, _i]),
-    'xps_ctc_loss_f32': (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    'xps_sumsq_f32_workspace': (_sz, [_i64]),
-    'xps_sumsq_f32': (_i, [_vp, _i64, _vp, _vp, _sz, _vp]),
-    'xps_adamw_f32': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _i, _vp]),
-    'xps_clip_adamw_f32': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _i, _vp, _sz, _vp]),
-    'xps_cnd_avg_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp]),
-    'xps_cnd_avg_f64': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp]),
-    'xps_colsum_f64_workspace': (_sz, [_i64, _i]),
-    'xps_colsum_f64': (_i, [_vp, _i, _i64, _i64, _i, _vp, _vp, _sz, _vp]),
-    'xps_xcov_f64_workspace': (_sz, [_i64, _i, _i]),
-    'xps_xcov_f64': (_i, [_vp, _i, _i64, _vp, _vp, _i, _i64, _vp, _vp, _i64, _i64, _i, _i, _vp, _sz, _vp]),
-    'xps_jacobi_f64_workspace': (_sz, [_i]),
-    'xps_jacobi_sweeps_f64': (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    'xps_jacobi_small_supported': (_i, [_i, _i, _i]),
-    'xps_chol_whiten_supported': (_i, [_i]),
-    'xps_chol_whiten_f64': (_i, [_vp, _i64, _i64, _d, _d, _vp, _i64, _i64, _vp, _i64, _i64, _i, _i, _vp, _vp]),
-    'xps_jacobi_small_f64': (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
-    'xps_apply_f64': (_i, [_vp, _i, _i64, _vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _vp]),
-    'xps_process_hg_f64_workspace': (_sz, [_i, _i, _i]),
-    'xps_process_hg_f64': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    'xps_pipe_frontend_f64_workspace': (_sz, [_i, _i, _i, _i]),
-    'xps_pipe_frontend_f64': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    'xps_hg_trials_f64_workspace': (_sz, [_i64, _i, _i, _i, _i]),
-    'xps_hg_trials_f64': (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i,
-                               _i, _vp, _vp, _sz, _vp]),
-    'xps_aug_time_shift_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    'xps_aug_time_mask_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'xps_aug_scale_f32': (_i, [_vp, _vp, _i64, _f, _vp]),
-    'xps_aug_jitter_f32': (_i, [_vp, _vp, _vp, _i64, _f, _vp]),
-    'xps_aug_time_warp_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    'xps_aug_trial_shift_f32': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    'xps_aug_trial_mask_f32': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
-    'xps_aug_trial_scale_f32': (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
-    'xps_aug_trial_warp_f32': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    'xps_ctc_greedy_decode': (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp]),
-    'xps_edit_distance_supported': (_i, [_i, _i]),
-    'xps_edit_distance_i64': (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _vp]),
-    'xps_rbf_from_gram_f64':(_i, [_vp, _i64, _vp, _vp, _i, _i, _d, _vp, _i64, _vp]),
-    'xps_svm_smo_f64_max_points': (_sz, []),
-    'xps_svm_smo_f64': (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _vp]),
-    'xps_bag_coef_scatter_f64': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp]),
-    'xps_bag_vote_f64': (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    'xps_dgemm_small': (_i, [_vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _i, _i, _i, _vp]),
-    'xps_dgemm_splitk_workspace': (_sz, [_i, _i, _i]),
-    'xps_dgemm_splitk': (_i, [_vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
-    'xps_lanczos_f64_workspace': (_sz, [_i]),
-    'xps_lanczos_f64': (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    'xps_cheb_filter_f64_workspace': (_sz, [_i, _i]),
-    'xps_cheb_filter_f64': (_i, [_vp, _i64, _i, _vp, _i, _i, _d, _d, _d, _vp, _vp, _sz, _vp]),
-    'xps_group_mean_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
-    'xps_group_mean_f64': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
-    'xps_group_mean_many_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    'xps_group_mean_many_f64': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    'xps_select_channels_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    'xps_select_channels_f64': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
-}
+
+_NAME = re.compile(r'\b(xps_[a-z0-9_]+)\s*\(')
+
+
+def _strip(src):
+    """Header text without its /* */ comments (the header has no // comments; a name in one would count as declared)."""
+    return re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+
+
+def _ctype(decl, fn, is_return=False):
+    """ctypes class of one C parameter or return type.  `const` and the parameter's name are noise; anything else the
+    header has not used before (a new type, an array declarator) raises, naming the function: nothing is guessed."""
+    words = re.sub(r'\bconst\b', ' ', decl).replace('*', ' * ').split()
+    what = ' '.join(words)
+    if not is_return and len(words) > 1 and words[-1] != '*':
+        if not re.fullmatch(r'[A-Za-z_]\w*', words.pop()):          # the parameter's name
+            raise XpsError(f'include/xps.h: {fn}: cannot read the parameter {what!r}')
+    base, stars = ' '.join(w for w in words if w != '*'), words.count('*')
+    if stars == 0 and base in _CTYPES:
+        return _CTYPES[base]
+    if stars == 1 and base == 'xps_rowmap':
+        return C.POINTER(RowMap)
+    if stars == 1 and base == 'char' and is_return:
+        return C.c_char_p
+    if stars and base in _POINTEES:                  # device pointers, host arrays of them, void**, xps_tn_problem*
+        return C.c_void_p
+    raise XpsError(f'include/xps.h: {fn}: no ctypes mapping for the C type in {what!r}')
+
+
+def parse_signatures(src):
+    """name -> (restype, [argtypes]) of every `ret xps_name(args);` in the header text `src`, /* */ comments and
+    preprocessor lines stripped.  Raises for a declaration _ctype cannot read and for an xps_ name followed by `(` that no
+    prototype was read for, so no entry point is bound wrongly or left unbound silently."""
+    src = re.sub(r'^[ \t]*#.*$', '', _strip(src), flags=re.M)
+    sigs = {}
+    for ret, fn, args in re.findall(r'([A-Za-z_][\w\s\*]*?)\b(xps_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', src):
+        args = [] if args.strip() in ('', 'void') else args.split(',')
+        sigs[fn] = (_ctype(ret, fn, is_return=True), [_ctype(a, fn) for a in args])
+    unread = sorted(set(_NAME.findall(src)) - set(sigs))
+    if unread:
+        raise XpsError(f'include/xps.h: no prototype could be read for {unread}')
+    return sigs
 
 
 def header_functions(path=HEADER_PATH):
     """Names of all functions declared in include/xps.h."""
     with open(path) as f:
-        src = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(xps_[a-z0-9_]+)\s*\(', src)))
+        return sorted(set(_NAME.findall(_strip(f.read()))))
+
+
+def _header_signatures():
+    if not os.path.exists(HEADER_PATH):
+        raise XpsError(f'{HEADER_PATH} is missing: the ctypes signatures of libxps.so are read from it')
+    with open(HEADER_PATH) as f:
+        return parse_signatures(f.read())
+
+
+SIGNATURES = _header_signatures()        # the header is the only place the argument types are written down
 
 
 def lib():

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import torch
 
+from .._dev import current_device, ptr, stream, workspace
 from .._lib import call, lib
 
 F64 = torch.float64
@@ -17,25 +18,8 @@ EPS = float(np.finfo(np.float64).eps)
 
 
 def device():
-    if not torch.cuda.is_available():
-        raise RuntimeError('cross_patient_speech_decoding_amd.alignment needs the MI355X: the HIP path has no '
-                           'CPU fallback')
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-_raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-_current_device = torch._C._cuda_getDevice if hasattr(torch._C, '_cuda_getDevice') else torch.cuda.current_device
-
-
-def _stream():
-    """Raw handle of torch's current stream (the C-level getter: ~0.3 us instead of ~10 us for the Stream object)."""
-    if _raw_stream is not None:
-        return _raw_stream(_current_device())
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ws(nbytes):
-    return torch.empty(int(nbytes), dtype=torch.uint8, device=device())
+    """The current device; raises where there is none (no CPU fallback)."""
+    return current_device('cross_patient_speech_decoding_amd.alignment')
 
 
 def to_device(x):
@@ -82,7 +66,7 @@ def cnd_avg_device(data_d, order, start):
     o = torch.from_numpy(order).to(data_d.device)
     s = torch.from_numpy(start).to(data_d.device)
     fn = 'xps_cnd_avg_f32' if data_d.dtype == torch.float32 else 'xps_cnd_avg_f64'
-    call(fn, data_d.data_ptr(), o.data_ptr(), s.data_ptr(), out.data_ptr(), n_cond, row_len, _stream())
+    call(fn, data_d.data_ptr(), o.data_ptr(), s.data_ptr(), out.data_ptr(), n_cond, row_len, stream())
     return out
 
 
@@ -92,8 +76,8 @@ def col_mean(X):
     n, d = X.shape
     out = torch.empty(d, dtype=F64, device=X.device)
     nb = lib().xps_colsum_f64_workspace(n, d)
-    ws = _ws(nb)
-    call('xps_colsum_f64', X.data_ptr(), _is32(X), X.stride(0), n, d, out.data_ptr(), ws.data_ptr(), nb, _stream())
+    ws = workspace(nb, device())
+    call('xps_colsum_f64', X.data_ptr(), _is32(X), X.stride(0), n, d, out.data_ptr(), ws.data_ptr(), nb, stream())
     return out / n
 
 
@@ -106,10 +90,10 @@ def xcov(A, B=None, mean_a=None, mean_b=None):
     db = B.shape[1]
     C = torch.empty(da, db, dtype=F64, device=A.device)
     nb = lib().xps_xcov_f64_workspace(n, da, db)
-    ws = _ws(nb)
-    call('xps_xcov_f64', A.data_ptr(), _is32(A), A.stride(0), None if mean_a is None else mean_a.data_ptr(),
-         B.data_ptr(), _is32(B), B.stride(0), None if mean_b is None else mean_b.data_ptr(),
-         C.data_ptr(), db, n, da, db, ws.data_ptr(), nb, _stream())
+    ws = workspace(nb, device())
+    call('xps_xcov_f64', A.data_ptr(), _is32(A), A.stride(0), ptr(mean_a),
+         B.data_ptr(), _is32(B), B.stride(0), ptr(mean_b),
+         C.data_ptr(), db, n, da, db, ws.data_ptr(), nb, stream())
     return C
 
 
@@ -123,12 +107,12 @@ def dgemm(A, B, ta=False, tb=False):
     if K >= 512 and ((M + 63) // 64) * ((N + 63) // 64) <= 64:
         # few output tiles, long contraction (the skinny products of the subspace iteration): split-K slabs + one reduce
         nb = lib().xps_dgemm_splitk_workspace(M, N, K)
-        ws = _ws(nb)
+        ws = workspace(nb, device())
         call('xps_dgemm_splitk', A.data_ptr(), A.stride(0), int(ta), B.data_ptr(), B.stride(0), int(tb), C.data_ptr(), N,
-             M, N, K, ws.data_ptr(), nb, _stream())
+             M, N, K, ws.data_ptr(), nb, stream())
         return C
     call('xps_dgemm_small', A.data_ptr(), A.stride(0), int(ta), B.data_ptr(), B.stride(0), int(tb), C.data_ptr(), N,
-         M, N, K, _stream())
+         M, N, K, stream())
     return C
 
 
@@ -139,9 +123,9 @@ def cheb_filter(Cd, A, deg, c, e, sigma1):
     n, m = A.shape
     out = torch.empty_like(A)
     nb = lib().xps_cheb_filter_f64_workspace(n, m)
-    ws = _ws(nb)
+    ws = workspace(nb, device())
     call('xps_cheb_filter_f64', Cd.data_ptr(), Cd.stride(0), n, A.data_ptr(), m, int(deg), float(c), float(e), float(sigma1),
-         out.data_ptr(), ws.data_ptr(), nb, _stream())
+         out.data_ptr(), ws.data_ptr(), nb, stream())
     return out
 
 
@@ -152,8 +136,8 @@ def apply(X, W, mean=None, out_f32=False):
     n, d_in = X2.shape
     d_out = W.shape[1]
     Y = torch.empty(n, d_out, dtype=torch.float32 if out_f32 else F64, device=X.device)
-    call('xps_apply_f64', X2.data_ptr(), _is32(X2), X2.stride(0), None if mean is None else mean.data_ptr(),
-         W.data_ptr(), W.stride(0), Y.data_ptr(), int(out_f32), d_out, n, d_in, d_out, _stream())
+    call('xps_apply_f64', X2.data_ptr(), _is32(X2), X2.stride(0), ptr(mean),
+         W.data_ptr(), W.stride(0), Y.data_ptr(), int(out_f32), d_out, n, d_in, d_out, stream())
     return Y.view(*X.shape[:-1], d_out)
 
 
@@ -171,8 +155,8 @@ def _jacobi(Wc, n_cols, m_rows, max_sweeps=40, tol=None, want_v=True):
         tol = max(1e-14, 4.0 * EPS * np.sqrt(max(m_rows, n_cols)) * np.log2(max(n_cols, 2)))
     Vc = torch.empty(n_cols, n_cols, dtype=F64, device=Wc.device) if want_v else None
     if lib().xps_jacobi_small_supported(m_rows, n_cols, int(want_v)):
-        call('xps_jacobi_small_f64', Wc.data_ptr(), Wc.stride(0), 0, None if Vc is None else Vc.data_ptr(), n_cols, 0,
-             m_rows, n_cols, 1, max_sweeps, tol, None, None, _stream())
+        call('xps_jacobi_small_f64', Wc.data_ptr(), Wc.stride(0), 0, ptr(Vc), n_cols, 0,
+             m_rows, n_cols, 1, max_sweeps, tol, None, None, stream())
         return Vc
     if want_v:
         Vc.copy_(torch.eye(n_cols, dtype=F64, device=Wc.device))
@@ -180,8 +164,8 @@ def _jacobi(Wc, n_cols, m_rows, max_sweeps=40, tol=None, want_v=True):
     done = 0
     while done < max_sweeps:
         k = 5 if done == 0 else 1
-        call('xps_jacobi_sweeps_f64', Wc.data_ptr(), Wc.stride(0), None if Vc is None else Vc.data_ptr(), n_cols, m_rows,
-             n_cols, k, off.data_ptr(), None, 0, _stream())
+        call('xps_jacobi_sweeps_f64', Wc.data_ptr(), Wc.stride(0), ptr(Vc), n_cols, m_rows,
+             n_cols, k, off.data_ptr(), None, 0, stream())
         done += k
         if off.item() <= tol:
             break
@@ -197,8 +181,8 @@ def jacobi_batched(Wb, want_v=True, max_sweeps=40, tol=None):
     if not lib().xps_jacobi_small_supported(m, n, int(want_v)):
         raise ValueError(f'jacobi_batched: {m} x {n} does not fit the single-workgroup kernel')
     Vb = torch.empty(batch, n, n, dtype=F64, device=Wb.device) if want_v else None
-    call('xps_jacobi_small_f64', Wb.data_ptr(), Wb.stride(1), Wb.stride(0), None if Vb is None else Vb.data_ptr(), n,
-         n * n, m, n, batch, max_sweeps, tol, None, None, _stream())
+    call('xps_jacobi_small_f64', Wb.data_ptr(), Wb.stride(1), Wb.stride(0), ptr(Vb), n,
+         n * n, m, n, batch, max_sweeps, tol, None, None, stream())
     return Vb
 
 
@@ -221,7 +205,7 @@ def chol_whiten_blocks(Gd, offs, scale, shift, LHS=None):
         call('xps_chol_whiten_f64', Gd.data_ptr() + o * (ld + 1) * 8, ld, n * (ld + 1), float(scale), float(shift),
              None if LHS is None else LHS.data_ptr() + o * (LHS.stride(0) + 1) * 8, 0 if LHS is None else LHS.stride(0),
              0 if LHS is None else n * (LHS.stride(0) + 1), S.data_ptr() + o * (S.stride(0) + 1) * 8, S.stride(0),
-             n * (S.stride(0) + 1), n, cnt, info.data_ptr() + 4 * b0, _stream())
+             n * (S.stride(0) + 1), n, cnt, info.data_ptr() + 4 * b0, stream())
     if int(info.abs().max().item()) != 0:
         return None
     return S
@@ -346,10 +330,10 @@ def _lanczos_bounds(C, steps=24):
     v = (v / torch.linalg.vector_norm(v)).contiguous()
     ab_d = torch.empty(2 * steps, dtype=F64, device=dev)
     nb = lib().xps_lanczos_f64_workspace(n)
-    ws = _ws(nb)
+    ws = workspace(nb, device())
     # (the whole recurrence is enqueued by one library call: 2 launches per step; the Python loop paid ~10 launches per step)
     call('xps_lanczos_f64', C.data_ptr(), C.stride(0), n, steps, v.data_ptr(), ab_d.data_ptr(), ab_d.data_ptr() + 8 * steps,
-         ws.data_ptr(), nb, _stream())
+         ws.data_ptr(), nb, stream())
     ab = ab_d.cpu().numpy()
     a, b = ab[:steps], ab[steps:]
     if not np.isfinite(ab).all():

@@ -25,6 +25,7 @@ from sklearn.base import BaseEstimator, ClassifierMixin
 from sklearn.utils import check_random_state
 from sklearn.utils.random import sample_without_replacement
 
+from .._dev import stream
 from .._lib import call, lib
 from ..alignment import _linalg as LA
 from .svm import SVC, _class_weights
@@ -178,7 +179,7 @@ class BaggingClassifier(ClassifierMixin, BaseEstimator):
             sq = torch.diagonal(G).contiguous()              # |x_i|^2: the Gram diagonal (libsvm: dot(x_i, x_i))
             K = torch.empty_like(G)
             call('xps_rbf_from_gram_f64', G.data_ptr(), G.stride(0), sq.data_ptr(), sq.data_ptr(), n, n, float(gamma), K.data_ptr(),
-                 K.stride(0), LA._stream())
+                 K.stride(0), stream())
         else:
             sq, K = None, G
         ints = np.concatenate([idx, off, npos, pair_a, pair_b, est_off]).astype(np.int32)       # one upload of all index lists
@@ -190,10 +191,10 @@ class BaggingClassifier(ClassifierMixin, BaseEstimator):
         rho = torch.empty(Q, dtype=torch.float64, device=dev)
         iters = torch.empty(Q, dtype=torch.int32, device=dev)
         call('xps_svm_smo_f64', K.data_ptr(), K.stride(0), idx_d.data_ptr(), off_d.data_ptr(), npos_d.data_ptr(), Q, max_pts,
-             cb_d.data_ptr(), float(est.tol), max_iter, alpha.data_ptr(), rho.data_ptr(), iters.data_ptr(), LA._stream())
+             cb_d.data_ptr(), float(est.tol), max_iter, alpha.data_ptr(), rho.data_ptr(), iters.data_ptr(), stream())
         coef = torch.empty(Q, n, dtype=torch.float64, device=dev)
         call('xps_bag_coef_scatter_f64', alpha.data_ptr(), idx_d.data_ptr(), off_d.data_ptr(), npos_d.data_ptr(), Q, n, coef.data_ptr(),
-             coef.stride(0), LA._stream())
+             coef.stride(0), stream())
         if est.kernel == 'linear':
             self._W, self._coef = LA.dgemm(coef, Xd), None  # (Q, d) weight vectors; the coefficients are not needed again
             self._Xd = None
@@ -241,7 +242,7 @@ class BaggingClassifier(ClassifierMixin, BaseEstimator):
         votes = torch.empty(m, self.n_classes_, dtype=torch.int32, device=dec.device)
         pred = torch.empty(m, dtype=torch.int32, device=dec.device)
         call('xps_bag_vote_f64', dec.data_ptr(), dec.stride(0), self._rho.data_ptr(), self._pair_a.data_ptr(), self._pair_b.data_ptr(),
-             self._est_off.data_ptr(), m, self._E, self.n_classes_, votes.data_ptr(), pred.data_ptr(), LA._stream())
+             self._est_off.data_ptr(), m, self._E, self.n_classes_, votes.data_ptr(), pred.data_ptr(), stream())
         return pred.cpu().numpy(), votes.cpu().numpy()
 
     def predict(self, X):

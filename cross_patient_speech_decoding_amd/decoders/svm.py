@@ -15,6 +15,7 @@ import numpy as np
 import torch
 from sklearn.base import BaseEstimator, ClassifierMixin
 
+from .._dev import stream
 from .._lib import call, lib
 from ..alignment import _linalg as LA
 
@@ -99,7 +100,7 @@ class SVC(ClassifierMixin, BaseEstimator):
             return G
         K = torch.empty_like(G)
         call('xps_rbf_from_gram_f64', G.data_ptr(), G.stride(0), na.data_ptr(), nb.data_ptr(), G.shape[0], G.shape[1], float(self._gamma),
-             K.data_ptr(), K.stride(0), LA._stream())
+             K.data_ptr(), K.stride(0), stream())
         return K
 
     # ------------------------------------------------------------------ fit
@@ -153,7 +154,7 @@ class SVC(ClassifierMixin, BaseEstimator):
         max_iter = int(self.max_iter) if self.max_iter and self.max_iter > 0 else max(10_000_000, 100 * max_pts)
         cb = torch.from_numpy(float(self.C) * cw[yi[idx]] * w[idx]).to(dev)
         call('xps_svm_smo_f64', K.data_ptr(), K.stride(0), idx_d.data_ptr(), off_d.data_ptr(), npos_d.data_ptr(), P, max_pts,
-             cb.data_ptr(), float(self.tol), max_iter, alpha.data_ptr(), rho.data_ptr(), iters.data_ptr(), LA._stream())
+             cb.data_ptr(), float(self.tol), max_iter, alpha.data_ptr(), rho.data_ptr(), iters.data_ptr(), stream())
         # signed dual coefficients of every pair scattered into a dense (P, n) matrix
         coef = torch.zeros(P, n, dtype=torch.float64, device=dev)
         sign = torch.ones(len(idx), dtype=torch.float64, device=dev)

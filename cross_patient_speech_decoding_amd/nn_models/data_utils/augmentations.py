@@ -10,8 +10,8 @@ arithmetic there); the goldens in tests/golden/augmentations.npz are float32."""
 import numpy as np
 import torch
 
+from ..._dev import need_gpu, ptr, stream
 from ..._lib import call
-from ..functional import _need_gpu, _ptr, _stream
 
 
 def _on_device(data):
@@ -23,7 +23,7 @@ def _on_device(data):
     if host and not torch.cuda.is_available():
         raise RuntimeError('cross_patient_speech_decoding_amd: the augmentation kernels need the MI355X (no CPU fallback)')
     x = data.to('cuda', dtype=torch.float32).contiguous()
-    _need_gpu(x)
+    need_gpu(x)
     return x, host, data.dtype
 
 
@@ -40,7 +40,7 @@ def time_warping(data, factor_range=(0.8, 1.2)):
     N, T, C = x.shape
     T2 = int(round(T * factor))                       # scipy.ndimage.zoom's output length
     out = torch.empty_like(x)
-    call('xps_aug_time_warp_f32', _ptr(x), _ptr(out), N, T, C, max(T2, 1), _stream())
+    call('xps_aug_time_warp_f32', ptr(x), ptr(out), N, T, C, max(T2, 1), stream())
     return _back(out, host, dt)
 
 
@@ -51,7 +51,7 @@ def time_masking(data, mask_ratio=0.1):
     x, host, dt = _on_device(data)
     N, T, C = x.shape
     out = torch.empty_like(x)
-    call('xps_aug_time_mask_f32', _ptr(x), _ptr(out), N, T, C, int(mask_start), int(mask_size), _stream())
+    call('xps_aug_time_mask_f32', ptr(x), ptr(out), N, T, C, int(mask_start), int(mask_size), stream())
     return _back(out, host, dt)
 
 
@@ -60,7 +60,7 @@ def time_shifting(data, shift_max=20):
     x, host, dt = _on_device(data)
     N, T, C = x.shape
     out = torch.empty_like(x)
-    call('xps_aug_time_shift_f32', _ptr(x), _ptr(out), N, T, C, int(shift), _stream())
+    call('xps_aug_time_shift_f32', ptr(x), ptr(out), N, T, C, int(shift), stream())
     return _back(out, host, dt)
 
 
@@ -70,7 +70,7 @@ def noise_jitter(data, noise_level=0.01):
     x, host, dt = _on_device(data)
     nz = noise.to('cuda', dtype=torch.float32).contiguous()
     out = torch.empty_like(x)
-    call('xps_aug_jitter_f32', _ptr(x), _ptr(nz), _ptr(out), x.numel(), float(noise_level), _stream())
+    call('xps_aug_jitter_f32', ptr(x), ptr(nz), ptr(out), x.numel(), float(noise_level), stream())
     return _back(out, host, dt)
 
 
@@ -78,5 +78,5 @@ def scaling(data, scale_range=(0.9, 1.1)):
     scale = np.random.uniform(*scale_range)
     x, host, dt = _on_device(data)
     out = torch.empty_like(x)
-    call('xps_aug_scale_f32', _ptr(x), _ptr(out), x.numel(), float(np.float32(scale)), _stream())
+    call('xps_aug_scale_f32', ptr(x), ptr(out), x.numel(), float(np.float32(scale)), stream())
     return _back(out, host, dt)

@@ -12,25 +12,10 @@ from typing import NamedTuple
 
 import torch
 
+from .._dev import need_gpu as _need_gpu, ptr as _ptr, ptr_array as _ptr_array, stream as _stream, workspace as _ws  # noqa: F401
 from .._lib import TnProblem, call, lib, rowmap
 
 _f32 = torch.float32
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-_raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-_current_device = torch._C._cuda_getDevice if hasattr(torch._C, '_cuda_getDevice') else torch.cuda.current_device
-
-
-def _stream():
-    """Raw handle of torch's current stream (the C-level getter: ~0.3 us instead of ~10 us for the Stream object)."""
-    if _raw_stream is not None:
-        return _raw_stream(_current_device())
-    return torch.cuda.current_stream().cuda_stream
-
 
 GEMM_PRECISIONS = {'fp32': 0, 'bf16x3': 1}
 
@@ -47,22 +32,6 @@ def set_gemm_precision(name):
 def get_gemm_precision():
     mode = lib().xps_get_gemm_precision()
     return {v: k for k, v in GEMM_PRECISIONS.items()}[mode]
-
-
-def _need_gpu(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError('cross_patient_speech_decoding_amd: tensors must live on the MI355X '
-                               '(cuda) device; the HIP path has no CPU fallback')
-
-
-def _ws(nbytes, device):
-    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-
-
-def _ptr_array(tensors):
-    arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-    return arr
 
 
 _memo_values = {}

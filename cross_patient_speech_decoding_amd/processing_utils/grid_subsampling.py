@@ -64,7 +64,8 @@ def select_channels_sweep(X, list_of_index_arrays):
     torch, host or device: a list of (N, T, len(idx)) DEVICE tensors, contiguous views of one slab, written by one launch
     that reads X once.  X is uploaded once; nothing synchronises.  ValueError (before any launch) for an empty list, an
     empty index array, an index outside [0, C) or X.ndim != 3."""
-    from ..alignment._linalg import _stream, to_device
+    from .._dev import stream
+    from ..alignment._linalg import to_device
     if X.ndim != 3:
         raise ValueError(f'select_channels_sweep: X must be (trials, time, channels), got {X.ndim} dimensions')
     if len(list_of_index_arrays) == 0:
@@ -83,5 +84,5 @@ def select_channels_sweep(X, list_of_index_arrays):
     S, Ltot = len(lists), int(start[-1])
     slab = torch.empty(N * T * Ltot, dtype=Xd.dtype, device=Xd.device)
     fn = 'xps_select_channels_f32' if Xd.dtype == torch.float32 else 'xps_select_channels_f64'
-    call(fn, Xd.data_ptr(), N, T, C, meta.data_ptr(), meta.data_ptr() + 4 * (S + 1), S, Ltot, slab.data_ptr(), _stream())
+    call(fn, Xd.data_ptr(), N, T, C, meta.data_ptr(), meta.data_ptr() + 4 * (S + 1), S, Ltot, slab.data_ptr(), stream())
     return [slab[N * T * int(a):N * T * int(b)].view(N, T, int(b - a)) for a, b in zip(start[:-1], start[1:])]

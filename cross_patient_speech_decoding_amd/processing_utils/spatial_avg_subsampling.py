@@ -68,7 +68,8 @@ def spatial_avg_sweep(data, list_of_avgIdxs):
     contiguous views of one slab, from ONE launch that reads ``data`` once (xps_group_mean_many_*).  ``data``
     (trials, X, Y, time), float32 or float64, numpy or torch, is uploaded once if it is on the host; nothing synchronises.
     Each tensor holds the bits spatial_avg_data gives for that grouping."""
-    from ..alignment._linalg import F64, _stream, to_device
+    from .._dev import stream
+    from ..alignment._linalg import F64, to_device
     if len(list_of_avgIdxs) == 0:
         raise ValueError('spatial_avg_sweep: no groupings')
     csr = _check(data, list_of_avgIdxs, 'spatial_avg_sweep')
@@ -82,7 +83,7 @@ def spatial_avg_sweep(data, list_of_avgIdxs):
     slab = torch.empty(N * T * Gtot, dtype=F64, device=d.device)
     p = meta.data_ptr()
     fn = 'xps_group_mean_many_f32' if d.dtype == torch.float32 else 'xps_group_mean_many_f64'
-    call(fn, d.data_ptr(), N, X * Y, T, p, p + 4 * (S + 1), p + 4 * (S + 1 + Gtot + 1), S, Gtot, slab.data_ptr(), _stream())
+    call(fn, d.data_ptr(), N, X * Y, T, p, p + 4 * (S + 1), p + 4 * (S + 1 + Gtot + 1), S, Gtot, slab.data_ptr(), stream())
     return [slab[N * T * int(a):N * T * int(b)].view(N, T, int(b - a)) for a, b in zip(gstart[:-1], gstart[1:])]
 
 
@@ -90,7 +91,8 @@ def spatial_avg_data(data, avgIdxs):
     """Mean of ``data`` (trials, X, Y, time) over each group of grid cells of ``avgIdxs`` -> (trials, time, groups) float64,
     the reference's bits (members added in order in the input's dtype, one division, widened).  numpy in -> numpy out, a
     device tensor in -> a device tensor out."""
-    from ..alignment._linalg import F64, _stream, like_input, to_device
+    from .._dev import stream
+    from ..alignment._linalg import F64, like_input, to_device
     (offsets, members), = _check(data, [avgIdxs], 'spatial_avg_data')
     d = to_device(data)
     N, X, Y, T = d.shape
@@ -98,5 +100,5 @@ def spatial_avg_data(data, avgIdxs):
     meta = torch.from_numpy(np.concatenate([offsets, members]).astype(np.int32)).to(d.device)
     out = torch.empty(N, T, G, dtype=F64, device=d.device)
     fn = 'xps_group_mean_f32' if d.dtype == torch.float32 else 'xps_group_mean_f64'
-    call(fn, d.data_ptr(), N, X * Y, T, meta.data_ptr(), meta.data_ptr() + 4 * (G + 1), G, out.data_ptr(), _stream())
+    call(fn, d.data_ptr(), N, X * Y, T, meta.data_ptr(), meta.data_ptr() + 4 * (G + 1), G, out.data_ptr(), stream())
     return like_input(out, data)

@@ -16,8 +16,8 @@ Precision: float32, the dtype the data modules hold (a float64 input is rounded,
 augmentations of nn_models/data_utils/augmentations.py (one draw per call) are a different family and are untouched."""
 import torch
 
+from .._dev import need_gpu, ptr, stream
 from .._lib import call
-from ..nn_models.functional import _need_gpu, _ptr, _stream
 
 
 # ---- the draws (host logic only: testable without the device) ------------------------------------------------------------
@@ -53,7 +53,7 @@ def _on_device(data, out):
     if host and not torch.cuda.is_available():
         raise RuntimeError('cross_patient_speech_decoding_amd: the augmentation kernels need the MI355X (no CPU fallback)')
     x = data.to('cuda', dtype=torch.float32).contiguous()
-    _need_gpu(x)
+    need_gpu(x)
     if out is None:
         res = torch.empty_like(x)
     else:
@@ -85,7 +85,7 @@ def time_warping(data, factor_range=(0.8, 1.2), out=None, draw_device=None):
     x, res, host, dt = _on_device(data, out)
     if B and int(T2.min()) < 1:
         raise ValueError('time_warping: a warp factor gives an empty intermediate sequence')
-    call('xps_aug_trial_warp_f32', _ptr(x), _ptr(res), B, T, x.shape[2], _ptr(_dev(T2, x, torch.int64)), _stream())
+    call('xps_aug_trial_warp_f32', ptr(x), ptr(res), B, T, x.shape[2], ptr(_dev(T2, x, torch.int64)), stream())
     return _back(res, out, host, dt)
 
 
@@ -95,8 +95,8 @@ def time_masking(data, mask_ratio=0.1, out=None, draw_device=None):
     B, T, _ = data.shape
     starts, mask_size = draw_mask_starts(B, T, mask_ratio)
     x, res, host, dt = _on_device(data, out)
-    call('xps_aug_trial_mask_f32', _ptr(x), _ptr(res), B, T, x.shape[2], _ptr(_dev(starts, x, torch.int64)), int(mask_size),
-         _stream())
+    call('xps_aug_trial_mask_f32', ptr(x), ptr(res), B, T, x.shape[2], ptr(_dev(starts, x, torch.int64)), int(mask_size),
+         stream())
     return _back(res, out, host, dt)
 
 
@@ -106,7 +106,7 @@ def time_shifting(data, shift_max=20, out=None, draw_device=None):
     B, T, _ = data.shape
     shifts = draw_shifts(B, draw_device or data.device, shift_max)
     x, res, host, dt = _on_device(data, out)
-    call('xps_aug_trial_shift_f32', _ptr(x), _ptr(res), B, T, x.shape[2], _ptr(_dev(shifts, x, torch.int64)), _stream())
+    call('xps_aug_trial_shift_f32', ptr(x), ptr(res), B, T, x.shape[2], ptr(_dev(shifts, x, torch.int64)), stream())
     return _back(res, out, host, dt)
 
 
@@ -116,7 +116,7 @@ def noise_jitter(data, noise_level=0.01, out=None, draw_device=None):
     noise = torch.randn_like(data) if draw_device is None else torch.randn(data.shape, dtype=data.dtype, device=draw_device)
     x, res, host, dt = _on_device(data, out)
     nz = _dev(noise, x, torch.float32)
-    call('xps_aug_jitter_f32', _ptr(x), _ptr(nz), _ptr(res), x.numel(), float(noise_level), _stream())
+    call('xps_aug_jitter_f32', ptr(x), ptr(nz), ptr(res), x.numel(), float(noise_level), stream())
     return _back(res, out, host, dt)
 
 
@@ -126,8 +126,8 @@ def scaling(data, scale_range=(0.9, 1.1), out=None, draw_device=None):
     B = data.size(0)
     scales = draw_scales(B, draw_device or data.device, scale_range)
     x, res, host, dt = _on_device(data, out)
-    call('xps_aug_trial_scale_f32', _ptr(x), _ptr(res), B, x.shape[1] * x.shape[2], _ptr(_dev(scales.reshape(-1), x, torch.float32)),
-         _stream())
+    call('xps_aug_trial_scale_f32', ptr(x), ptr(res), B, x.shape[1] * x.shape[2], ptr(_dev(scales.reshape(-1), x, torch.float32)),
+         stream())
     return _back(res, out, host, dt)
 
 

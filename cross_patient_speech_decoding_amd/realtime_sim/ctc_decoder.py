@@ -7,6 +7,7 @@ is no CPU fallback."""
 import numpy as np
 import torch
 
+from .._dev import ptr, stream, workspace
 from .._lib import call, lib
 
 BEAM_MAX, CLASSES_MAX, CANDIDATES_MAX = 128, 64, 8192
@@ -33,7 +34,7 @@ def greedy_decode_device(scores, blank=0, time_major=False):
     tokens = torch.empty(B, T, dtype=torch.int64, device=scores.device)
     lengths = torch.empty(B, dtype=torch.int64, device=scores.device)
     call('xps_ctc_greedy_decode', scores.data_ptr(), int(scores.dtype == torch.float32), int(st), int(sb), T, B, Cn, int(blank),
-         tokens.data_ptr(), lengths.data_ptr(), torch.cuda.current_stream(scores.device).cuda_stream)
+         tokens.data_ptr(), lengths.data_ptr(), stream(scores.device))
     return tokens, lengths
 
 
@@ -84,10 +85,10 @@ def _beam_device(log_probs, input_lengths, beam_size, blank, from_logits):
     plen = torch.empty(B, dtype=torch.int64, device=dev)
     nll = torch.empty(B, dtype=torch.float64, device=dev)
     ws_bytes = int(lib().xps_ctc_beam_workspace(B, T, int(beam_size), S))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    ws = workspace(max(ws_bytes, 1), dev)
     call('xps_ctc_beam_f64', x.data_ptr(), int(x.dtype == torch.float32), B, T, S,
-         None if lens is None else lens.data_ptr(), int(blank), int(beam_size), int(bool(from_logits)), prefix.data_ptr(),
-         plen.data_ptr(), nll.data_ptr(), ws.data_ptr(), ws_bytes, torch.cuda.current_stream(dev).cuda_stream)
+         ptr(lens), int(blank), int(beam_size), int(bool(from_logits)), prefix.data_ptr(),
+         plen.data_ptr(), nll.data_ptr(), ws.data_ptr(), ws_bytes, stream(dev))
     return prefix, plen, nll
 
 

@@ -29,16 +29,12 @@ import numpy as np
 import torch
 from sklearn.model_selection import KFold, StratifiedKFold, train_test_split
 
+from .._dev import current_device
 from ..alignment import PCA, AlignCCA
 from .realtime_pipeline import feature_map_from
 
 FOLD_KEYS = ('train_data', 'train_labels', 'val_data', 'val_labels', 'test_data', 'test_labels')
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError('cross_patient_speech_decoding_amd: the CTC data modules need the MI355X (no CPU fallback)')
-    return torch.device('cuda', torch.cuda.current_device())
+_WHO = 'cross_patient_speech_decoding_amd: CTC data module setup'        # named by the "needs the MI355X" error
 
 
 def _f32(x):
@@ -111,7 +107,7 @@ def reduce_to_latent_space(data, pca=None, n_components=30, low_thresh=5):
     data = torch.as_tensor(data)
     shapes = data.shape
     host = not data.is_cuda
-    data_2d = data.reshape(-1, shapes[-1]).to(_device())
+    data_2d = data.reshape(-1, shapes[-1]).to(current_device(_WHO))
     if pca is not None:
         dr = pca
     else:
@@ -206,7 +202,7 @@ class _CTCModule:
 
     # ---- one split: reduce, align, pool, augment -------------------------------------------------------------------
     def _build(self, key, tr, va):
-        dev = _device()
+        dev = current_device(_WHO)
         take = lambda t, i: t[torch.as_tensor(i, dtype=torch.int64)]                          # noqa: E731
         tgt, tgt_lab = take(self.train_data_tgt, tr).to(dev), take(self.train_labels_tgt, tr)
         val = None if va is None else take(self.train_data_tgt, va).to(dev)
@@ -274,7 +270,7 @@ class _CTCModule:
         return self.data_path / (f'rnn_realtime_fold{key}.npz' if self.cv else 'rnn_realtime.npz')
 
     def _store(self, key, **arrays):
-        dev = _device()
+        dev = current_device(_WHO)
         self._folds[key] = {n: (None if a is None else a.to(dev).contiguous()) for n, a in arrays.items()}
         if self.save_folds:
             os.makedirs(self.data_path, exist_ok=True)
@@ -282,7 +278,7 @@ class _CTCModule:
 
     def load_folds(self):
         """Re-populate the cache from the ``.npz`` files ``save_folds=True`` wrote (a missing validation split stays None)."""
-        dev = _device()
+        dev = current_device(_WHO)
         for key in range(self.n_folds if self.cv else 1):
             with np.load(self._file(key)) as f:
                 self._folds[key] = {n: (torch.as_tensor(f[n]).to(dev) if n in f.files else None) for n in FOLD_KEYS}

@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from ..nn_models import functional as XF
 from ..nn_models._lightning import LightningModule
+from .._dev import current_device, stream
 from .._lib import call as _call, rowmap  # noqa: F401
 from .ctc_decoder import greedy_decode_batch, greedy_decode_device  # noqa: F401
 
@@ -78,7 +79,7 @@ def edit_distance_device(pred, pred_lengths, targets, target_lengths):
         raise ValueError(f'{pl.numel()} / {tl.numel()} lengths for {B} pairs')
     dist = torch.empty(B, dtype=torch.int64, device=dev)
     _call('xps_edit_distance_i64', pred.data_ptr(), P, pl.data_ptr(), targets.data_ptr(), L, tl.data_ptr(), B, P, L,
-          dist.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+          dist.data_ptr(), stream(dev))
     return dist
 
 
@@ -90,15 +91,12 @@ def per_device(tokens, lengths, targets, target_lengths):
     return dist.sum().double() / total * 100
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError('cross_patient_speech_decoding_amd: the edit-distance kernel needs the MI355X (no CPU fallback)')
-    return torch.device('cuda', torch.cuda.current_device())
+_WHO = 'cross_patient_speech_decoding_amd: the edit-distance kernel'        # named by the "needs the MI355X" error
 
 
 def edit_distance(a, b):
     """Levenshtein distance of two label sequences (torchaudio.functional.edit_distance), on the device."""
-    dev = _device()
+    dev = current_device(_WHO)
     a = torch.as_tensor([int(v) for v in a], dtype=torch.int64, device=dev).reshape(1, -1)
     b = torch.as_tensor([int(v) for v in b], dtype=torch.int64, device=dev).reshape(1, -1)
     return int(edit_distance_device(a, [a.size(1)], b, [b.size(1)])[0])
@@ -106,7 +104,7 @@ def edit_distance(a, b):
 
 def calc_PER(decoded, targets, target_lengths):
     """Phoneme error rate in percent (reference :303-324): decoded = list of 1-D LongTensors (greedy_decode_batch)."""
-    dev = _device()
+    dev = current_device(_WHO)
     lengths = torch.tensor([int(p.numel()) for p in decoded], dtype=torch.int64)
     width = int(lengths.max()) if len(decoded) else 0
     tokens = torch.zeros(len(decoded), width, dtype=torch.int64, device=dev)
@@ -283,7 +281,7 @@ class StreamingDecoder:
 
     @torch.no_grad()
     def _body(self, par):
-        st = torch.cuda.current_stream().cuda_stream
+        st = stream()
         src, dst = self.hbuf[par], self.hbuf[par ^ 1]
         inp, k = self.window, self.K
         for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(self._params):

@@ -17,6 +17,7 @@ with fewer electrodes is padded with bad channels and zero map rows.  There is n
 import numpy as np
 import torch
 
+from .._dev import ptr, stream, workspace
 from .._lib import call, lib
 from .ctc_decoder import check_beam_sizes
 from .realtime_nn_model import _layer_params
@@ -156,7 +157,7 @@ class RealtimePipeline:
         self._bins = torch.zeros(B, self.stride, C, self.Tn, dtype=_F64, device=dev)
         self._power = torch.zeros(B, kmax, C, dtype=_F64, device=dev)
         self._ws_bytes = int(lib().xps_pipe_frontend_f64_workspace(B, C, self.Tn, self.bands))
-        self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=dev)
+        self._ws = workspace(self._ws_bytes, dev)
         self.wbuf = torch.zeros(2, S, self.K, dtype=torch.float32, device=dev)             # ping-pong windows
         self.hbuf = torch.zeros(2, self.L, S, self.H, dtype=torch.float32, device=dev)     # ping-pong hidden state
         self._logits = torch.zeros(S, self.n_classes, dtype=torch.float32, device=dev)
@@ -242,7 +243,7 @@ class RealtimePipeline:
             raise RuntimeError(f'stream {s} ran more than max_steps = {self.max_steps} beam-search steps')
         self._call('xps_ctc_beam_readout', self._bstate.data_ptr(), self._bstate_bytes, self.B, self.beam_size,
                    self.max_steps, s, self._bprefix.data_ptr(), self._blen.data_ptr(), self._bnll.data_ptr(),
-                   torch.cuda.current_stream().cuda_stream)
+                   stream())
         return self._bprefix[:int(self._blen)].clone()
 
     def beam_nll(self, s):
@@ -266,19 +267,17 @@ class RealtimePipeline:
 
     # ---- launches --------------------------------------------------------------------------------------------------
     def _frontend(self, bins, k, st):
-        ptr = lambda t: None if t is None else t.data_ptr()
         self._call('xps_pipe_frontend_f64', bins.data_ptr(), self.B, k, self.C, self.Tn, self._good.data_ptr(),
                    self._b.data_ptr(), ptr(self._a), self.bands, self.taps, ptr(self._zi), self._power.data_ptr(),
                    self._ws.data_ptr(), self._ws_bytes, st)
 
     def _shift(self, k, src, dst, st):
-        ptr = lambda t: None if t is None else t.data_ptr()
         self._call('xps_window_shift_f32', self._power.data_ptr(), k, self.C, ptr(self._W), ptr(self._c),
                    src.data_ptr(), dst.data_ptr(), self.win, self.d, self.B, st)
 
     @torch.no_grad()
     def _body(self, par):
-        st = torch.cuda.current_stream().cuda_stream
+        st = stream()
         self._frontend(self._bins, self.stride, st)
         self._shift(self.stride, self.wbuf[par], self.wbuf[par ^ 1], st)
         src, dst = self.hbuf[par], self.hbuf[par ^ 1]
@@ -309,7 +308,7 @@ class RealtimePipeline:
         if k == 0:
             return
         bd = torch.as_tensor(bins, dtype=_F64).to(self.dev).contiguous()
-        st = torch.cuda.current_stream().cuda_stream
+        st = stream()
         self._frontend(bd, k, st)
         cur, nxt = self.wbuf[self.parity], self.wbuf[self.parity ^ 1]
         self._shift(k, cur, nxt, st)

@@ -13,23 +13,17 @@ is not defined) agrees to rounding.  There is no CPU fallback."""
 import numpy as np
 import torch
 
+from .._dev import current_device, ptr, stream, workspace
 from .._lib import call, lib
 
 _F64 = torch.float64
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        raise RuntimeError('realtime_processing needs the MI355X: the HIP path has no CPU fallback')
-    return torch.device('cuda', torch.cuda.current_device())
+_WHO = 'realtime_processing'        # named by the "needs the MI355X" error
 
 
 def _up(x):
-    return None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).to(_dev())
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+    if x is None:
+        return None
+    return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).to(current_device(_WHO))
 
 
 def lfilter_zi(b, a):
@@ -52,7 +46,7 @@ def _run(data, b=None, a=None, zi=None, good=None, do_car=True, want='power'):
     """One launch.  ``want``: 'car' | 'filtered' | 'power'.  Returns (result ndarray, updated zi ndarray or None)."""
     data = np.asarray(data, dtype=np.float64)
     Cn, Tn = data.shape
-    dev = _dev()
+    dev = current_device(_WHO)
     d = _up(data)
     bands = 0 if b is None else b.shape[0]
     taps = 1 if b is None else b.shape[1]
@@ -63,10 +57,9 @@ def _run(data, b=None, a=None, zi=None, good=None, do_car=True, want='power'):
     filt = torch.empty(Cn, Tn, max(bands, 1), dtype=_F64, device=dev) if want == 'filtered' else None
     power = torch.empty(Cn, dtype=_F64, device=dev) if want == 'power' else None
     nbytes = lib().xps_process_hg_f64_workspace(Cn, Tn, max(bands, 1))
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
+    ws = workspace(nbytes, dev)
     call('xps_process_hg_f64', ptr(d), Cn, Tn, ptr(gd), ptr(bd), ptr(ad), bands, taps, ptr(zd), int(do_car), ptr(car),
-         ptr(filt), ptr(power), ptr(ws), nbytes, _stream())
+         ptr(filt), ptr(power), ptr(ws), nbytes, stream())
     out = car if want == 'car' else (filt if want == 'filtered' else power)
     return out.cpu().numpy(), (None if zd is None else zd.cpu().numpy())
 
@@ -161,12 +154,11 @@ def _hg_trials(raw, b, a, bands, taps, lengths=None, good=None, zi=None, want_st
         n_maps = n_maps if W is None else W.shape[0]
         feats = torch.empty(N, n_bins, d, dtype=torch.float32, device=dev)
     nbytes = int(lib().xps_hg_trials_f64_workspace(N, n_bins, Cn, Tn, bands))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
+    ws = workspace(nbytes, dev)
     call('xps_hg_trials_f64', raw.data_ptr(), int(raw.dtype == torch.float32), N, n_bins, Cn, Tn, ptr(lengths), ptr(good),
          int(good is not None and good.dim() == 2), ptr(b), ptr(a), bands, taps, ptr(zi), int(zi is not None and zi.dim() == 4),
          ptr(state), ptr(power), ptr(W), ptr(c), ptr(map_of_trial), n_maps, d, ptr(feats), ws.data_ptr(), nbytes,
-         torch.cuda.current_stream(dev).cuda_stream)
+         stream(dev))
     return power, state, feats
 
 
@@ -184,7 +176,7 @@ def _trials_on_device(data, n_chan=None, bin_samples=None):
     data = _check_trials(data, n_chan, bin_samples)
     if data.dtype not in (torch.float32, torch.float64):
         data = data.to(_F64)
-    return data.to(_dev()).contiguous()
+    return data.to(current_device(_WHO)).contiguous()
 
 
 def _trial_lengths(lengths, N, n_bins):

@@ -43,14 +43,14 @@ def dev_tensor(a):
 # ------------------------------------------------------------------------------------------------ 1. the vote kernel
 def run_vote(dec, ld, rho, pa, pb, est_off, m, E, k):
     import torch
+    from cross_patient_speech_decoding_amd import _dev
     from cross_patient_speech_decoding_amd._lib import call
-    from cross_patient_speech_decoding_amd.alignment import _linalg as LA
     dec_d, rho_d = dev_tensor(dec), dev_tensor(rho)
     pa_d, pb_d, eo_d = dev_tensor(pa.astype(np.int32)), dev_tensor(pb.astype(np.int32)), dev_tensor(est_off.astype(np.int32))
     votes = torch.full((m, max(k, 1)), -7, dtype=torch.int32, device=dec_d.device)
     pred = torch.full((m,), -7, dtype=torch.int32, device=dec_d.device)
     call('xps_bag_vote_f64', dec_d.data_ptr(), ld, rho_d.data_ptr(), pa_d.data_ptr(), pb_d.data_ptr(), eo_d.data_ptr(), m, E, k,
-         votes.data_ptr(), pred.data_ptr(), LA._stream())
+         votes.data_ptr(), pred.data_ptr(), _dev.stream())
     torch.cuda.synchronize()
     return votes.cpu().numpy(), pred.cpu().numpy()
 
@@ -134,6 +134,7 @@ def test_coef_scatter_equals_numpy(Q, n):
     """Ragged problems (a problem of 2 points among them where the row allows it), a leading dimension beyond n whose padding
     stays untouched, every element of the Q x n block written (the output starts as NaN); n = 4101 spans three column chunks."""
     import torch
+    from cross_patient_speech_decoding_amd import _dev
     from cross_patient_speech_decoding_amd._lib import call
     from cross_patient_speech_decoding_amd.alignment import _linalg as LA
     rng = np.random.default_rng(Q * 1000 + n)
@@ -154,7 +155,7 @@ def test_coef_scatter_equals_numpy(Q, n):
     coef = torch.full((Q, ldc), float('nan'), dtype=torch.float64, device=LA.device())
     a_d, i_d, o_d, p_d = dev_tensor(alpha), dev_tensor(idx), dev_tensor(off), dev_tensor(npos)
     call('xps_bag_coef_scatter_f64', a_d.data_ptr(), i_d.data_ptr(), o_d.data_ptr(), p_d.data_ptr(), Q, n, coef.data_ptr(), ldc,
-         LA._stream())
+         _dev.stream())
     torch.cuda.synchronize()
     got = coef.cpu().numpy()
     np.testing.assert_array_equal(got[:, :n], want)

@@ -213,6 +213,7 @@ def test_smo_launches_at_the_lds_resident_limit():
     more is refused by the argument check."""
     import ctypes as C
     import torch
+    from cross_patient_speech_decoding_amd import _dev
     from cross_patient_speech_decoding_amd._lib import XpsError, call, lib
     from cross_patient_speech_decoding_amd.alignment import _linalg as LA
     n = int(lib().xps_svm_smo_f64_max_points())
@@ -231,7 +232,7 @@ def test_smo_launches_at_the_lds_resident_limit():
     rho = torch.empty(1, dtype=torch.float64, device=dev)
     iters = torch.empty(1, dtype=torch.int32, device=dev)
     args = (K.data_ptr(), K.stride(0), idx.data_ptr(), off.data_ptr(), npos.data_ptr(), 1)
-    tail = (cb.data_ptr(), 1e-3, 200, alpha.data_ptr(), rho.data_ptr(), iters.data_ptr(), LA._stream())
+    tail = (cb.data_ptr(), 1e-3, 200, alpha.data_ptr(), rho.data_ptr(), iters.data_ptr(), _dev.stream())
     call('xps_svm_smo_f64', *args, n, *tail)
     torch.cuda.synchronize()
     assert 0 < int(iters[0]) <= 200 and bool(torch.isfinite(alpha).all()) and float(alpha.sum()) > 0
