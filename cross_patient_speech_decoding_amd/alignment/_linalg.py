@@ -48,6 +48,17 @@ def _is32(t):
     return int(t.dtype == torch.float32)
 
 
+def _rows(t):
+    """`t` as the kernels read a matrix: element (i, j) at data_ptr + i * stride(0) + j.  A row-strided view (a block of columns
+    of a wider matrix) already is that and is passed as it is, with its stride(0) as the leading dimension; a view whose last
+    stride is not 1 (a transpose, every second column) is copied."""
+    return t if t.stride(-1) == 1 else t.contiguous()
+
+
+def _vec(t):
+    return None if t is None else t.contiguous()
+
+
 # ------------------------------------------------------------------------------------ k1
 def condition_index(keys):
     """Sorted unique string keys + CSR (order, start) of the trials of each condition, trials in
@@ -73,6 +84,7 @@ def cnd_avg_device(data_d, order, start):
 # ------------------------------------------------------------------------------------ k2
 def col_mean(X):
     """Column means (float64) of an (n, d) device matrix."""
+    X = _rows(X)
     n, d = X.shape
     out = torch.empty(d, dtype=F64, device=X.device)
     nb = lib().xps_colsum_f64_workspace(n, d)
@@ -86,6 +98,9 @@ def xcov(A, B=None, mean_a=None, mean_b=None):
     B = A if B is None else B
     if B is A and mean_b is None:
         mean_b = mean_a
+    Ar = _rows(A)
+    A, B = Ar, (Ar if B is A else _rows(B))
+    mean_a, mean_b = _vec(mean_a), _vec(mean_b)
     n, da = A.shape
     db = B.shape[1]
     C = torch.empty(da, db, dtype=F64, device=A.device)
@@ -99,7 +114,7 @@ def xcov(A, B=None, mean_a=None, mean_b=None):
 
 def dgemm(A, B, ta=False, tb=False):
     """op(A) @ op(B) for small float64 device matrices."""
-    A, B = A.contiguous(), B.contiguous()
+    A, B = _rows(A), _rows(B)
     M = A.shape[1] if ta else A.shape[0]
     K = A.shape[0] if ta else A.shape[1]
     N = B.shape[0] if tb else B.shape[1]
@@ -119,7 +134,7 @@ def dgemm(A, B, ta=False, tb=False):
 def cheb_filter(Cd, A, deg, c, e, sigma1):
     """Y_deg of the scaled Chebyshev recurrence on the block A (n x m) with the symmetric operator Cd -- `deg` products
     enqueued by ONE library call (xps_cheb_filter_f64: per product a split-K launch + a reduce that applies the three-term update)."""
-    A = A.contiguous()
+    A, Cd = A.contiguous(), _rows(Cd)
     n, m = A.shape
     out = torch.empty_like(A)
     nb = lib().xps_cheb_filter_f64_workspace(n, m)
@@ -131,8 +146,8 @@ def cheb_filter(Cd, A, deg, c, e, sigma1):
 
 def apply(X, W, mean=None, out_f32=False):
     """(X - mean) @ W over all rows of X (..., d_in) -> (..., d_out).  W float64 (d_in, d_out)."""
-    W = W.contiguous()
-    X2 = X.reshape(-1, X.shape[-1])
+    W, mean = _rows(W), _vec(mean)
+    X2 = _rows(X.reshape(-1, X.shape[-1]))
     n, d_in = X2.shape
     d_out = W.shape[1]
     Y = torch.empty(n, d_out, dtype=torch.float32 if out_f32 else F64, device=X.device)
@@ -322,12 +337,11 @@ def _lanczos_bounds(C, steps=24):
     reorthogonalisation: only the two extreme Ritz values are used): extreme Ritz value -/+ its residual bound
     |beta_j s_j|, widened by 2 % of the width.  The recurrence runs on the device without synchronising; the
     steps x steps tridiagonal matrix is diagonalised by the small device Jacobi."""
-    C = C.contiguous()
+    C = _rows(C)
     n = C.shape[0]
     steps = min(steps, n)
     dev = C.device
-    v = torch.sin(0.7 * torch.arange(1, n + 1, dtype=F64, device=dev)) + 0.01
-    v = (v / torch.linalg.vector_norm(v)).contiguous()
+    v = torch.sin(0.7 * torch.arange(1, n + 1, dtype=F64, device=dev)) + 0.01      # (xps_lanczos_f64 starts from v / ||v||)
     ab_d = torch.empty(2 * steps, dtype=F64, device=dev)
     nb = lib().xps_lanczos_f64_workspace(n)
     ws = workspace(nb, device())

@@ -808,13 +808,33 @@ static __global__ __launch_bounds__(1024) void lanczos_step_kernel(const double*
     if (tid == 0) { alpha[j] = a; beta[j] = b; }
 }
 
+// v = v0 / ||v0||, vp = 0: the start of the recurrence, on the device (the norm never visits the host).  ONE workgroup, fixed order.
+static __global__ __launch_bounds__(1024) void lanczos_start_kernel(const double* __restrict__ v0, int n, double* __restrict__ v,
+                                                                    double* __restrict__ vp) {
+    __shared__ double red[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double nn = 0.0;
+    for (int i = tid; i < n; i += 1024) nn += v0[i] * v0[i];
+    nn = wave_sum(nn);
+    if (lane == 0) red[wave] = nn;
+    __syncthreads();
+    double s = 0.0;
+    for (int i = 0; i < 16; ++i) s += red[i];
+    const double nrm = sqrt(s);
+    for (int i = tid; i < n; i += 1024) {
+        v[i] = v0[i] / nrm;
+        vp[i] = 0.0;
+    }
+}
+
 extern "C" size_t xps_lanczos_f64_workspace(int n) {
     if (n <= 0) return 16;
     return ((size_t)dgemm_splits(n, 1, n) + 3) * n * sizeof(double) + 16;
 }
 
-// `steps` Lanczos steps on the symmetric n x n matrix C from the start vector v0 (normalised here): alpha[steps], beta[steps]
-// (device arrays) = the diagonal / off-diagonal of the tridiagonal matrix; enqueued by this one call (2 launches per step).
+// `steps` Lanczos steps on the symmetric n x n matrix C from the start vector v0 (any non-zero length: normalised here, on the
+// device): alpha[steps], beta[steps] (device arrays) = the diagonal / off-diagonal of the tridiagonal matrix; enqueued by this one
+// call (one launch for the start, 2 per step).
 extern "C" int xps_lanczos_f64(const double* C, int64_t ldc, int n, int steps, const double* v0, double* alpha, double* beta,
                                void* workspace, size_t workspace_bytes, void* stream) {
     XPS_CHECK_ARG(C && v0 && alpha && beta && n >= 1 && steps >= 1, "bad argument");
@@ -829,11 +849,7 @@ extern "C" int xps_lanczos_f64(const double* C, int64_t ldc, int n, int steps, c
     double* v = slabs + (long long)splits * n;
     double* vp = v + n;
     double* w = vp + n;
-    if (hipMemcpyAsync(v, v0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess ||
-        hipMemsetAsync(vp, 0, (size_t)n * sizeof(double), st) != hipSuccess) {
-        xps_set_error("xps_lanczos_f64: copy failed");
-        return XPS_E_HIP;
-    }
+    hipLaunchKernelGGL(lanczos_start_kernel, dim3(1), dim3(1024), 0, st, v0, n, v, vp);
     Mat64 cm{C, (long long)ldc, nullptr, 0};
     for (int j = 0; j < steps; ++j) {
         Mat64 vm{v, 1, nullptr, 0};

@@ -619,9 +619,13 @@ int xps_dgemm_splitk(const double* A, int64_t lda, int ta, const double* B, int6
 /* Chebyshev filter of an n x m block A (row-major, leading dimension m) by the symmetric n x n matrix C: the scaled three-term
  * recurrence of the top-k eigensolve behind AlignMCCA.fit (alignment/AlignMCCA.py:152-153 hands the generalised eigenproblem
  * to mvlearn / scipy.linalg.eigh): Y_1 = (C A - c A) sigma1 / e, Y_{j+1} = (C Y_j - c Y_j) 2 sigma_{j+1} / e - sigma_j sigma_{j+1} Y_{j-1},
- * sigma_{j+1} = 1 / (2 / sigma1 - sigma_j); `deg` products, all enqueued by this one call; out (n x m) receives Y_deg.       */
-/* `steps` Lanczos steps (no reorthogonalisation) on the symmetric n x n matrix C from v0 / ||v0||: alpha[steps], beta[steps]
- * (device arrays) = diagonal / off-diagonal of the tridiagonal matrix whose extreme Ritz values bound the spectrum for the filter */
+ * sigma_{j+1} = 1 / (2 / sigma1 - sigma_j); `deg` >= 1 products, all enqueued by this one call; out (n x m, leading dimension m)
+ * receives Y_deg and may not be A (refused: XPS_E_INVALID); C has leading dimension ldc >= n, e > 0.  Each product is summed as
+ * xps_dgemm_splitk sums it; the reduce of its slabs applies the three-term update.                                          */
+/* `steps` Lanczos steps (no reorthogonalisation) on the symmetric n x n matrix C (leading dimension ldc) from v0 / ||v0||: v0 (n,
+ * device) may have any non-zero length, it is normalised on the device inside the call (no host synchronisation; a zero v0 gives
+ * NaN).  alpha[steps], beta[steps] (device arrays) = diagonal / off-diagonal of the tridiagonal matrix whose extreme Ritz values
+ * bound the spectrum for the filter */
 size_t xps_lanczos_f64_workspace(int n);
 int xps_lanczos_f64(const double* C, int64_t ldc, int n, int steps, const double* v0, double* alpha, double* beta,
                     void* workspace, size_t workspace_bytes, void* stream);
