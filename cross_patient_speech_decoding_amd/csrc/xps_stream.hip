@@ -20,21 +20,24 @@ __device__ inline float wave_sum(float v) {
 template <int SB>
 __device__ inline void dot_rows(const float* __restrict__ wrow, const float* __restrict__ x, int K, int ldx, int lane,
                                 float (&acc)[SB]) {
-    // wrow: one weight row (K floats, 16-byte aligned when K % 4 == 0); x: SB input rows
+    // wrow: one weight row (K floats, 16-byte aligned when K % 4 == 0); x: SB input rows.
+    // The FMAs are written out: left to the compiler, the contraction of w.x * v.x + w.y * v.y + ... came out differently for
+    // the streams of one launch (the streams are packed in pairs and either product may be the rounded one) and for the
+    // template widths, so a stream's bits depended on its row and on B.
     if ((K & 3) == 0) {
         for (int k = lane * 4; k < K; k += 256) {
             const float4 w = *reinterpret_cast<const float4*>(wrow + k);
 #pragma unroll
             for (int s = 0; s < SB; ++s) {
                 const float4 v = *reinterpret_cast<const float4*>(x + (long long)s * ldx + k);
-                acc[s] += w.x * v.x + w.y * v.y + w.z * v.z + w.w * v.w;
+                acc[s] += fmaf(w.w, v.w, fmaf(w.z, v.z, fmaf(w.y, v.y, w.x * v.x)));
             }
         }
     } else {
         for (int k = lane; k < K; k += 64) {
             const float w = wrow[k];
 #pragma unroll
-            for (int s = 0; s < SB; ++s) acc[s] += w * x[(long long)s * ldx + k];
+            for (int s = 0; s < SB; ++s) acc[s] = fmaf(w, x[(long long)s * ldx + k], acc[s]);
         }
     }
 }
@@ -82,9 +85,9 @@ __global__ __launch_bounds__(256) void gru_cell_gemv_kernel(const float* __restr
         if (lane == 0 && s < B) {
             const float r = sigmoidf_acc(v[0] + b_ih[j] + v[3] + b_hh[j]);
             const float z = sigmoidf_acc(v[1] + b_ih[H + j] + v[4] + b_hh[H + j]);
-            const float n = tanhf(v[2] + b_ih[2 * H + j] + r * (v[5] + b_hh[2 * H + j]));
+            const float n = tanhf(fmaf(r, v[5] + b_hh[2 * H + j], v[2] + b_ih[2 * H + j]));
             const float hp = h_prev[(long long)s * H + j];
-            h_new[(long long)s * H + j] = n + z * (hp - n);
+            h_new[(long long)s * H + j] = fmaf(z, hp - n, n);
         }
     }
 }

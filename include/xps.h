@@ -297,7 +297,11 @@ int xps_decoder_bwd_f32(const float* dlogits, const float* hs, const float* save
 /* Streaming (batch-1 .. 8 streams) inference for the realtime decoder (realtime_sim/realtime_nn_model.py
  * :153-170, one window per call): weight-streaming GEMV kernels, one wave per output row.
  *   x, h_prev, h_new, out are [S][.] with S = 1, 2, 4 or 8 rows ALLOCATED (S = B rounded up to a power
- *   of two); only the first B rows are written.  h_new must not alias h_prev.                       */
+ *   of two); only the first B rows are written.  h_new must not alias h_prev.  The rows B .. S-1 of
+ *   x and h_prev are read (any values, NaN included) and reach no live row.  A stream's output bits
+ *   depend on its own input row alone: not on the row it occupies, not on B.  x and W (x and w_ih,
+ *   h_prev and w_hh) must be 16-byte aligned when K (H) is a multiple of 4; otherwise any float
+ *   alignment is taken.                                                                            */
 int xps_gemv_f32(const float* x, const float* W, const float* bias, float* out, int N, int K, int B,
                  void* stream);
 int xps_gru_cell_gemv_f32(const float* x, int K, const float* w_ih, const float* w_hh, const float* b_ih,

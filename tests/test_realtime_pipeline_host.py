@@ -32,6 +32,35 @@ def test_pipeline_entry_points_reject_bad_arguments(lib):
     assert lib.xps_ctc_collapse_f32(p, 11, 0, p, p, p, 16, 9, None) == -1
 
 
+def test_stream_entry_points_reject_bad_arguments(lib):
+    a, b, c, d, e, f, g, h = (C.c_void_p(4096 + 64 * i) for i in range(8))       # eight distinct 16-byte aligned addresses
+    off = lambda p: C.c_void_p(p.value + 4)
+
+    def refused(rc, name, word):
+        assert rc == -1
+        msg = lib.xps_last_error()
+        assert name in msg and word in msg, msg
+
+    gemv = lambda x, W, K=8, B=1: lib.xps_gemv_f32(x, W, None, c, 4, K, B, None)
+    refused(gemv(off(a), b), b'xps_gemv_f32', b'aligned')
+    refused(gemv(a, off(b)), b'xps_gemv_f32', b'aligned')
+    refused(gemv(a, b, B=0), b'xps_gemv_f32', b'streams')
+    refused(gemv(a, b, B=9), b'xps_gemv_f32', b'streams')
+    refused(gemv(None, b), b'xps_gemv_f32', b'bad argument')
+
+    def cell(x=a, w_ih=b, w_hh=c, h_prev=f, h_new=g, K=8, H=8, B=1):
+        return lib.xps_gru_cell_gemv_f32(x, K, w_ih, w_hh, d, e, h_prev, h_new, H, B, None)
+    name = b'xps_gru_cell_gemv_f32'
+    refused(cell(x=off(a)), name, b'x and w_ih')
+    refused(cell(w_ih=off(b)), name, b'x and w_ih')
+    refused(cell(h_prev=off(f), K=3), name, b'h and w_hh')
+    refused(cell(w_hh=off(c), K=3), name, b'h and w_hh')
+    refused(cell(B=0), name, b'streams')
+    refused(cell(B=9), name, b'streams')
+    refused(cell(h_new=f), name, b'alias')
+    refused(cell(H=0), name, b'bad argument')
+
+
 def test_feature_map_from_folds_affine_stages():
     from cross_patient_speech_decoding_amd.realtime_sim import feature_map_from
     rng = np.random.default_rng(0)
