@@ -61,7 +61,7 @@ __global__ __launch_bounds__(64) void ctc_kernel(const float* __restrict__ logit
     }
     for (int s = lane; s < CTC_MAXS + 2; s += 64) { row[0][s] = NEG_INF; row[1][s] = NEG_INF; }
     __syncthreads();
-    float nll = INFINITY;
+    float nll = Lb == 0 ? 0.f : INFINITY;       // no frames: the empty target has the one (empty) alignment, as in torch
     if (Tb > 0) {
         // ---- alpha ----
         for (int s = lane; s < S; s += 64) {
@@ -149,13 +149,14 @@ __global__ __launch_bounds__(64) void ctc_kernel(const float* __restrict__ logit
     }
 }
 
-// single block: mean over the batch of nll_b / max(L_b, 1), fixed order
+// single block: mean over the batch of nll_b / max(L_b, 1), fixed order; L_b clamped to Lmax as in ctc_kernel
 __global__ __launch_bounds__(256) void ctc_mean_kernel(const float* __restrict__ nll, const long long* __restrict__ tg_len,
-                                                       int B, float* __restrict__ loss) {
+                                                       int B, int Lmax, float* __restrict__ loss) {
     __shared__ double sh[256];
     double a = 0.0;
     for (int b = threadIdx.x; b < B; b += 256) {
-        const long long L = tg_len[b];
+        long long L = tg_len[b];
+        L = L > Lmax ? Lmax : L;
         a += (double)nll[b] / (double)(L > 1 ? L : 1);
     }
     sh[threadIdx.x] = a;
@@ -194,7 +195,7 @@ extern "C" int xps_ctc_loss_f32(const float* logits, const int64_t* targets, int
                        blank, zero_infinity, nll, dlogits, ws_alpha, ws_lse, Smax);
     XPS_CHECK_LAUNCH();
     hipLaunchKernelGGL(ctc_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, nll, (const long long*)target_lengths, B,
-                       loss);
+                       max_target_len, loss);
     XPS_CHECK_LAUNCH();
     return XPS_OK;
 }

@@ -1353,6 +1353,9 @@ class CTCLossFn(torch.autograd.Function):
         if not input_lengths.is_cuda and int(input_lengths.max()) > T:         # torch's own check (host lengths only)
             raise RuntimeError(f'Expected input_lengths to have value at most {T}, but got value '
                                f'{int(input_lengths.max())}')
+        if not target_lengths.is_cuda and target_lengths.numel() and int(target_lengths.max()) > targets.shape[1]:
+            raise RuntimeError(f'Expected tensor to have size at least {int(target_lengths.max())} at dimension 1, but '
+                               f'got size {tuple(targets.shape)}')          # torch's own check (host lengths only)
         tg = targets.to(device=dev, dtype=torch.int64).contiguous()
         il = input_lengths.to(device=dev, dtype=torch.int64).contiguous()
         tl = target_lengths.to(device=dev, dtype=torch.int64).contiguous()
@@ -1377,6 +1380,8 @@ class CTCLossFn(torch.autograd.Function):
 
 
 def ctc_loss(logits_tm, targets, input_lengths, target_lengths, blank=0, zero_infinity=True):
+    if not torch.is_grad_enabled():         # needs_input_grad ignores no_grad: detached, the kernel gets no gradient buffer
+        logits_tm = logits_tm.detach()
     return CTCLossFn.apply(logits_tm, targets, input_lengths, target_lengths, blank, zero_infinity)
 
 

@@ -464,7 +464,24 @@ int xps_time_mean_bwd_f32(const float* dout, float* dz, int T, int B, int F, voi
  * nn.CTCLoss(blank, reduction='mean', zero_infinity) on log_softmax(logits)).  logits [T][B][C] TIME-major raw
  * scores (the log-softmax is fused); targets [B][target_stride] int64 (padded); lengths int64 [B].
  * nll [B] per-sample negative log-likelihood; loss[0] = mean_b(nll_b / max(L_b, 1)); dlogits (optional, [T][B][C])
- * = d loss[0] / d logits.  One launch for the batch; workspace holds the alpha lattice.                          */
+ * = d loss[0] / d logits.  One launch for the batch; workspace holds the alpha lattice.
+ * Contract (tests/test_gpu_ctc_loss.py pins every line of it):
+ *   - Sizes: T, B, C >= 1, 0 <= blank < C, 0 <= max_target_len <= 511 (2 L + 1 states are held in LDS),
+ *     target_stride >= max_target_len; else XPS_E_INVALID before any launch, nothing written.  A workspace below
+ *     xps_ctc_loss_f32_workspace(T, B, max_target_len) bytes: XPS_E_WORKSPACE, nothing written.  The kernel stays inside
+ *     those bytes and needs no initial contents.
+ *   - Lengths are clamped on the device: Tb = clamp(input_lengths[b], 0, T), L = clamp(target_lengths[b], 0,
+ *     max_target_len), and the clamped L is also the loss's divisor.  Only targets[b][0 .. L) is read: the cells past a
+ *     sample's length and the stride padding may hold anything.  Labels in live cells must lie in 0 .. C-1 (the caller's
+ *     contract; the kernel only keeps them from addressing outside the row).
+ *   - Tb == 0: nll = 0 when L == 0 (the empty alignment, as torch), +inf otherwise; the sample's gradient is zero.
+ *   - An infinite nll (no alignment fits): with zero_infinity nll[b] = 0 and the sample's gradient is zero; without,
+ *     nll[b] = loss[0] = +inf and the sample's gradient rows t < Tb are unspecified (NaN in torch).  The other samples'
+ *     nll and gradient rows do not change either way.
+ *   - Every element of dlogits is written; the rows t >= Tb of a sample are zero.  dlogits == NULL: nll and loss only,
+ *     the same bits.
+ *   - nll[b] depends on sample b alone, dlogits[.][b][.] on sample b and on B through the factor 1 / (B max(L, 1)).
+ *   - Logits are finite; -inf logits are unspecified (torch's own gradient is NaN there).                          */
 size_t xps_ctc_loss_f32_workspace(int T, int B, int max_target_len);
 int xps_ctc_loss_f32(const float* logits, const int64_t* targets, int64_t target_stride,
                      const int64_t* input_lengths, const int64_t* target_lengths, int T, int B, int C,
