@@ -8,6 +8,7 @@
 // order, so alpha agrees to rounding, not bit for bit.  Latency-bound small-problem code: a problem of n points costs
 // O(n) iterations of five barriers.
 #include "xps_common.h"
+#include "xps_svm_rbf.h"
 
 namespace {
 
@@ -50,13 +51,17 @@ __device__ inline double block_max(double a, double* scratch) {
     return r;
 }
 
-// problem p: points idx[off[p] .. off[p + 1]), the first npos[p] of them carry y = +1, the others y = -1
-__global__ __launch_bounds__(SVM_THREADS) void svm_smo_kernel(const double* __restrict__ K, long long ldk, const int* __restrict__ idx,
+// problem p: points idx[off[p] .. off[p + 1]), the first npos[p] of them carry y = +1, the others y = -1.  kbase / kld (both NULL
+// or both set): problem p works on the matrix that starts at element kbase[p] of K with leading dimension kld[p]
+// (xps_svm_smo_multi_f64: the folds and gamma values of a grid search pose their problems to one launch)
+__global__ __launch_bounds__(SVM_THREADS) void svm_smo_kernel(const double* __restrict__ K, long long ldk, const long long* __restrict__ kbase,
+                                                              const long long* __restrict__ kld, const int* __restrict__ idx,
                                                               const int* __restrict__ off, const int* __restrict__ npos, const double* __restrict__ cbound,
                                                               double eps, int max_iter, double* __restrict__ alpha_out,
                                                               double* __restrict__ rho_out, int* __restrict__ iters_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int p = blockIdx.x, tid = threadIdx.x;
+    if (kbase) { K += kbase[p]; ldk = kld[p]; }
     const int o0 = off[p], n = off[p + 1] - o0, np = npos[p];
     double* alpha = reinterpret_cast<double*>(smem_raw);
     double* G = alpha + n;
@@ -177,7 +182,7 @@ __global__ __launch_bounds__(256) void rbf_from_gram_kernel(const double* __rest
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)m * n) return;
     const int i = (int)(idx / n), j = (int)(idx % n);
-    K[(long long)i * ldk + j] = exp(-gamma * (na[i] + nb[j] - 2.0 * G[(long long)i * ldg + j]));
+    K[(long long)i * ldk + j] = xps_rbf_from_gram(gamma, na[i], nb[j], G[(long long)i * ldg + j]);
 }
 
 }  // namespace
@@ -197,17 +202,40 @@ extern "C" int xps_rbf_from_gram_f64(const double* G, int64_t ldg, const double*
 constexpr size_t SVM_LDS_LIMIT = 160 * 1024 - 1024, SVM_LDS_FIXED = 64 + 128;
 extern "C" size_t xps_svm_smo_f64_max_points(void) { return (SVM_LDS_LIMIT - SVM_LDS_FIXED) / 28; }
 
+namespace {
+int svm_smo_launch(const char* who, const double* K, long long ldk, const long long* kbase, const long long* kld, const int* idx, const int* off,
+                   const int* npos, int nprob, int max_points, const double* cbound, double eps, int max_iter, double* alpha, double* rho,
+                   int* iters, void* stream) {
+    const int lds = max_points * 28 + 64;
+    static const bool ok = hipFuncSetAttribute((const void*)svm_smo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SVM_LDS_LIMIT) == hipSuccess;
+    if (!ok && lds > 64 * 1024) { xps_set_error("%s: cannot raise the dynamic LDS limit", who); return XPS_E_HIP; }
+    hipLaunchKernelGGL(svm_smo_kernel, dim3(nprob), dim3(SVM_THREADS), lds, (hipStream_t)stream, K, ldk, kbase, kld, idx, off, npos, cbound, eps,
+                       max_iter, alpha, rho, iters);
+    hipError_t e_ = hipGetLastError();
+    if (e_ != hipSuccess) { xps_set_error("%s: launch failed: %s", who, hipGetErrorString(e_)); return XPS_E_HIP; }
+    return XPS_OK;
+}
+}  // namespace
+
 extern "C" int xps_svm_smo_f64(const double* K, int64_t ldk, const int* idx, const int* off, const int* npos, int nprob, int max_points,
                                const double* cbound, double eps, int max_iter, double* alpha, double* rho, int* iters, void* stream) {
     XPS_CHECK_ARG(K && idx && off && npos && cbound && alpha && rho && iters, "null argument");
     XPS_CHECK_ARG(nprob >= 0 && eps > 0.0 && max_iter > 0, "bad parameter");
     XPS_CHECK_ARG(max_points >= 1 && (size_t)max_points <= xps_svm_smo_f64_max_points(), "a binary problem exceeds the LDS-resident limit");
     if (nprob == 0) return XPS_OK;
-    const int lds = max_points * 28 + 64;
-    static const bool ok = hipFuncSetAttribute((const void*)svm_smo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SVM_LDS_LIMIT) == hipSuccess;
-    if (!ok && lds > 64 * 1024) { xps_set_error("xps_svm_smo_f64: cannot raise the dynamic LDS limit"); return XPS_E_HIP; }
-    hipLaunchKernelGGL(svm_smo_kernel, dim3(nprob), dim3(SVM_THREADS), lds, (hipStream_t)stream, K, (long long)ldk, idx, off, npos, cbound, eps,
-                       max_iter, alpha, rho, iters);
-    XPS_CHECK_LAUNCH();
-    return XPS_OK;
+    return svm_smo_launch(__func__, K, (long long)ldk, nullptr, nullptr, idx, off, npos, nprob, max_points, cbound, eps, max_iter, alpha, rho,
+                          iters, stream);
+}
+
+// xps_svm_smo_f64 with a matrix per problem: the same kernel, the same iterates
+extern "C" int xps_svm_smo_multi_f64(const double* K, const int64_t* kbase, const int64_t* kld, const int* idx, const int* off, const int* npos,
+                                     int nprob, int max_points, const double* cbound, double eps, int max_iter, double* alpha, double* rho,
+                                     int* iters, void* stream) {
+    XPS_CHECK_ARG(K && kbase && kld && idx && off && npos && cbound && alpha && rho && iters, "null argument");
+    XPS_CHECK_ARG(nprob >= 0 && eps > 0.0 && max_iter > 0, "bad parameter");
+    XPS_CHECK_ARG(max_points >= 1 && (size_t)max_points <= xps_svm_smo_f64_max_points(), "a binary problem exceeds the LDS-resident limit");
+    if (nprob == 0) return XPS_OK;
+    static_assert(sizeof(long long) == sizeof(int64_t), "kbase / kld are read as long long");
+    return svm_smo_launch(__func__, K, 0, reinterpret_cast<const long long*>(kbase), reinterpret_cast<const long long*>(kld), idx, off, npos,
+                          nprob, max_points, cbound, eps, max_iter, alpha, rho, iters, stream);
 }

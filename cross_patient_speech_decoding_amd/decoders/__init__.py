@@ -2,3 +2,4 @@ from .cross_pt_decoders import (crossPtDecoder, crossPtDecoder_jointDimRed, cros
                                 crossPtDecoder_sepAlign, crossPtDecoder_sepDimRed)
 from .svm import SVC  # noqa: F401,E402
 from .bagging import BaggingClassifier  # noqa: F401,E402
+from .search import SVCSearchCV  # noqa: F401,E402

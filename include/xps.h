@@ -629,6 +629,35 @@ int xps_bag_coef_scatter_f64(const double* alpha, const int* idx, const int* off
                              double* coef, int64_t ldc, void* stream);
 int xps_bag_vote_f64(const double* dec, int64_t ld, const double* rho, const int* pair_a, const int* pair_b, const int* est_off,
                      int m, int E, int k, int* votes, int* pred, void* stream);
+/* Cross-validated SVC grid search (GridSearchCV / BayesSearchCV over SVC(kernel='rbf', class_weight='balanced') behind DimRedReshape,
+ * scripts/aligned_decode_svm_ncv.py:398-402,422-425): every fold's training set is a sub-block of one kernel matrix, every gamma an
+ * element-wise map of one Gram matrix, every C a bound vector, and a fold's held-out rows are rows of the same matrix.
+ * xps_rbf_multi_from_gram_f64: K + g * kstride (m x n, leading dimension ldk) = exp(-gammas[g] (na[i] + nb[j] - 2 G[i][j])) for g < M;
+ * gammas is a DEVICE array, each element of G is read once, and every matrix equals xps_rbf_from_gram_f64's for that gamma bit for bit.
+ * xps_svm_smo_multi_f64: xps_svm_smo_f64 with a matrix per problem: problem p works on the matrix that starts at element kbase[p] of
+ * K with leading dimension kld[p] (device arrays); the same kernel, the same iterates.
+ * xps_svm_cv_score_f64: model s < S (a candidate on a fold) owns the problems mod_off[s] .. mod_off[s + 1]) in the idx / off / npos /
+ * alpha / rho layout of the SMO entry with the class indices pair_a[q] < pair_b[q], the square matrix of mn[s] rows that starts at
+ * element mbase[s] of K with leading dimension mld[s], the held-out rows tst[tst_off[s] .. tst_off[s + 1]) (row indices into its
+ * matrix) and their true class indices ytrue[...].  dec(r, q) = sum_t +-alpha[off[q] + t] K_s[r][idx[off[q] + t]] - rho[q] (+ for
+ * t < npos[q], the convention of xps_bag_coef_scatter_f64); q votes pair_a[q] where dec > 0 STRICTLY, else pair_b[q]; the prediction
+ * is the first maximum of the k vote counts (libsvm).  Outputs: pred[tst_off[s] + i] (int32), conf[s][true][pred] (S x k x k int32,
+ * every element written, zeros for a model without held-out rows), and, unless dec_out is NULL, dec_out[(tst_off[s] + i) * ldd +
+ * (q - mod_off[s])] (ldd >= the largest problem count of a model).  mod_off and tst_off (S + 1 ints each) are HOST arrays: the call
+ * checks that they ascend from a value >= 0 and copies them into ws (DEVICE, xps_svm_cv_score_f64_workspace(S) bytes) on the stream.
+ * Nothing outside a model's matrix is dereferenced: a point index outside [0, mn[s]) adds no term; a held-out row outside it gets
+ * pred = -1, decisions of 0 and no count; a true class outside [0, k) is not counted.  k must be in 2..64.  Fixed summation order,
+ * integer votes and counts, no atomics: the result does not depend on the grid.                                                  */
+int xps_rbf_multi_from_gram_f64(const double* G, int64_t ldg, const double* na, const double* nb, int m, int n, const double* gammas,
+                                int M, double* K, int64_t ldk, int64_t kstride, void* stream);
+int xps_svm_smo_multi_f64(const double* K, const int64_t* kbase, const int64_t* kld, const int* idx, const int* off, const int* npos,
+                          int nprob, int max_points, const double* cbound, double eps, int max_iter, double* alpha, double* rho,
+                          int* iterations, void* stream);
+size_t xps_svm_cv_score_f64_workspace(int S);
+int xps_svm_cv_score_f64(const double* K, const int64_t* mbase, const int64_t* mld, const int* mn, const int* idx, const int* off,
+                         const int* npos, const double* alpha, const double* rho, const int* pair_a, const int* pair_b,
+                         const int* mod_off, const int* tst, const int* ytrue, const int* tst_off, int S, int k, int* pred, int* conf,
+                         double* dec_out, int64_t ldd, void* ws, size_t ws_bytes, void* stream);
 /* small dense float64 GEMM  C = op(A) op(B)  (row-major, op = transpose flag) */
 int xps_dgemm_small(const double* A, int64_t lda, int ta, const double* B, int64_t ldb, int tb,
                     double* C, int64_t ldc, int M, int N, int K, void* stream);
