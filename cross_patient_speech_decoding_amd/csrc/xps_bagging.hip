@@ -5,6 +5,7 @@
 //   bag_vote_kernel          decision values (m x Q) -> per-estimator libsvm vote -> ensemble vote counts and prediction.
 // Both are integer / copy work: no floating-point sums, no atomics, results independent of the launch geometry.
 #include "xps_common.h"
+#include "xps_wave_first_max.h"
 
 namespace {
 
@@ -38,15 +39,6 @@ __global__ __launch_bounds__(BAG_THREADS) void bag_coef_scatter_kernel(const dou
 }
 
 // ---- vote ---------------------------------------------------------------------------------------------------------------
-// first maximum over the 64 lanes of (value, index): the larger value, on equal values the SMALLER index
-__device__ inline void wave_first_max(int& v, int& c) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int ov = __shfl_xor(v, o), oc = __shfl_xor(c, o);
-        if (ov > v || (ov == v && oc < c)) { v = ov; c = oc; }
-    }
-}
-
 // One workgroup per test row.  The estimators are taken in groups whose problems fit the LDS stage (VOTE_STAGE winners, one byte
 // each; an estimator has at most 64 * 63 / 2 = 2016 problems, so a group is never empty):
 //   1. all 256 threads read the group's decision values -- consecutive problems of one row, i.e. whole lines -- with rho and the

@@ -206,6 +206,12 @@ namespace {
 int svm_smo_launch(const char* who, const double* K, long long ldk, const long long* kbase, const long long* kld, const int* idx, const int* off,
                    const int* npos, int nprob, int max_points, const double* cbound, double eps, int max_iter, double* alpha, double* rho,
                    int* iters, void* stream) {
+    // the argument checks of both entry points, reported under the entry's name
+    auto refuse = [who](const char* msg) -> int { xps_set_error("%s: %s", who, msg); return XPS_E_INVALID; };
+    if (!(K && idx && off && npos && cbound && alpha && rho && iters)) return refuse("null argument");
+    if (!(nprob >= 0 && eps > 0.0 && max_iter > 0)) return refuse("bad parameter");
+    if (!(max_points >= 1 && (size_t)max_points <= xps_svm_smo_f64_max_points())) return refuse("a binary problem exceeds the LDS-resident limit");
+    if (nprob == 0) return XPS_OK;
     const int lds = max_points * 28 + 64;
     static const bool ok = hipFuncSetAttribute((const void*)svm_smo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SVM_LDS_LIMIT) == hipSuccess;
     if (!ok && lds > 64 * 1024) { xps_set_error("%s: cannot raise the dynamic LDS limit", who); return XPS_E_HIP; }
@@ -219,10 +225,6 @@ int svm_smo_launch(const char* who, const double* K, long long ldk, const long l
 
 extern "C" int xps_svm_smo_f64(const double* K, int64_t ldk, const int* idx, const int* off, const int* npos, int nprob, int max_points,
                                const double* cbound, double eps, int max_iter, double* alpha, double* rho, int* iters, void* stream) {
-    XPS_CHECK_ARG(K && idx && off && npos && cbound && alpha && rho && iters, "null argument");
-    XPS_CHECK_ARG(nprob >= 0 && eps > 0.0 && max_iter > 0, "bad parameter");
-    XPS_CHECK_ARG(max_points >= 1 && (size_t)max_points <= xps_svm_smo_f64_max_points(), "a binary problem exceeds the LDS-resident limit");
-    if (nprob == 0) return XPS_OK;
     return svm_smo_launch(__func__, K, (long long)ldk, nullptr, nullptr, idx, off, npos, nprob, max_points, cbound, eps, max_iter, alpha, rho,
                           iters, stream);
 }
@@ -231,10 +233,7 @@ extern "C" int xps_svm_smo_f64(const double* K, int64_t ldk, const int* idx, con
 extern "C" int xps_svm_smo_multi_f64(const double* K, const int64_t* kbase, const int64_t* kld, const int* idx, const int* off, const int* npos,
                                      int nprob, int max_points, const double* cbound, double eps, int max_iter, double* alpha, double* rho,
                                      int* iters, void* stream) {
-    XPS_CHECK_ARG(K && kbase && kld && idx && off && npos && cbound && alpha && rho && iters, "null argument");
-    XPS_CHECK_ARG(nprob >= 0 && eps > 0.0 && max_iter > 0, "bad parameter");
-    XPS_CHECK_ARG(max_points >= 1 && (size_t)max_points <= xps_svm_smo_f64_max_points(), "a binary problem exceeds the LDS-resident limit");
-    if (nprob == 0) return XPS_OK;
+    XPS_CHECK_ARG(kbase && kld, "null argument");
     static_assert(sizeof(long long) == sizeof(int64_t), "kbase / kld are read as long long");
     return svm_smo_launch(__func__, K, 0, reinterpret_cast<const long long*>(kbase), reinterpret_cast<const long long*>(kld), idx, off, npos,
                           nprob, max_points, cbound, eps, max_iter, alpha, rho, iters, stream);

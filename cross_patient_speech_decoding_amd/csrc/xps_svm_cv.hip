@@ -7,6 +7,7 @@
 // The score kernel sums each decision in a fixed order and counts in integers: no atomics, results independent of the launch geometry.
 #include "xps_common.h"
 #include "xps_svm_rbf.h"
+#include "xps_wave_first_max.h"
 
 namespace {
 
@@ -27,15 +28,6 @@ __global__ __launch_bounds__(256) void rbf_multi_from_gram_kernel(const double* 
 // ---- scoring --------------------------------------------------------------------------------------------------------------
 constexpr int CV_THREADS = 256;
 constexpr int CV_WAVES = CV_THREADS / 64;
-
-// first maximum over the 64 lanes of (value, index): the larger value, on equal values the SMALLER index
-__device__ inline void wave_first_max(int& v, int& c) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int ov = __shfl_xor(v, o), oc = __shfl_xor(c, o);
-        if (ov > v || (ov == v && oc < c)) { v = ov; c = oc; }
-    }
-}
 
 // One workgroup of four waves per model s.  Held-out rows are taken four at a time, wave w the row i0 + w.  For each problem q of
 // the model the lanes stride over its points (alpha and idx coalesced, K gathered inside the one row), every lane adds its terms

@@ -16,7 +16,8 @@ predict  one upload of the test rows, one decision product (linear: X W^T; rbf: 
          ``xps_bag_vote_f64`` launch, download of ``pred`` and ``votes``.
 
 The bootstrap samples are sklearn's, draw for draw (``bagging_sample_indices``), so for the same ``random_state`` the ensemble is
-the one sklearn's bagging would train.  There is no CPU fallback."""
+the one sklearn's bagging would train.  Each estimator's problems are posed by the builder ``SVC.fit`` uses, and all are solved by
+the same driver (decoders/_ovo.py).  There is no CPU fallback."""
 import numbers
 
 import numpy as np
@@ -26,9 +27,10 @@ from sklearn.utils import check_random_state
 from sklearn.utils.random import sample_without_replacement
 
 from .._dev import stream
-from .._lib import call, lib
+from .._lib import call, lib  # noqa: F401  (lib: stubbed with call by the host tests that allow no device work before a refusal)
 from ..alignment import _linalg as LA
-from .svm import SVC, _class_weights
+from . import _ovo
+from .svm import SVC
 
 MAX_INT = np.iinfo(np.int32).max            # sklearn.ensemble._bagging.MAX_INT
 
@@ -104,31 +106,6 @@ class BaggingClassifier(ClassifierMixin, BaseEstimator):
             raise ValueError('n_estimators must be a positive integer')
         self.estimator._check_settings()
 
-    def _problems(self, yi, k, weights, cw):
-        """Index lists of all class-pair problems (host): estimator-major, libsvm's pair order inside an estimator, class members
-        in original order, zero-weight points left out; a class an estimator lost takes its pairs with it."""
-        C = float(self.estimator.C)
-        by_class = [np.flatnonzero(yi == c).astype(np.int32) for c in range(k)]
-        idx, cb, sizes, npos, pair_a, pair_b, est_off = [], [], [], [], [], [], [0]
-        for w in weights:
-            members = [m[w[m] > 0] for m in by_class]
-            bounds = [C * cw[c] * w[m] for c, m in enumerate(members)]
-            present = [c for c in range(k) if len(members[c])]
-            if len(present) < 2:
-                raise ValueError(f'The number of classes has to be greater than one; got {len(present)} class')
-            for i, a in enumerate(present):
-                for b in present[i + 1:]:
-                    idx += [members[a], members[b]]
-                    cb += [bounds[a], bounds[b]]
-                    sizes.append(len(members[a]) + len(members[b]))
-                    npos.append(len(members[a]))
-                    pair_a.append(a)
-                    pair_b.append(b)
-            est_off.append(len(sizes))
-        off = np.concatenate([[0], np.cumsum(sizes)])
-        return (np.concatenate(idx), np.concatenate(cb), off, np.asarray(npos), np.asarray(pair_a), np.asarray(pair_b),
-                np.asarray(est_off))
-
     def fit(self, X, y, sample_weight=None):
         self._check_settings()
         est = self.estimator
@@ -160,52 +137,31 @@ class BaggingClassifier(ClassifierMixin, BaseEstimator):
                 mask[s] = True
                 weights.append(np.where(mask, base_w, 0.0))
         # everything that SVC.fit derives from the X / y it is handed is derived from the WHOLE X / y, as under sklearn's bagging
-        gamma = est._gamma_value(X)
-        cw = _class_weights(est.class_weight, classes, yi)
-        idx, cb, off, npos, pair_a, pair_b, est_off = self._problems(yi, k, weights, cw)
-        Q = len(npos)
-        max_pts = int(np.diff(off).max())
-        limit = int(lib().xps_svm_smo_f64_max_points())
-        if max_pts > limit:
-            raise ValueError(f'a class pair has {max_pts} samples; the LDS-resident solver takes {limit}')
-        max_iter = int(est.max_iter) if est.max_iter and est.max_iter > 0 else max(10_000_000, 100 * max_pts)
+        gamma = _ovo.gamma_value(est.kernel, est.gamma, X)
+        cw = _ovo.class_weights(est.class_weight, classes, yi)
+        probs = [_ovo.pair_problems(yi, np.arange(n), cw, w) for w in weights]      # estimator-major; one estimator's as SVC.fit's
+        idx, npos, pair_a, pair_b, sizes = (np.concatenate([p[key] for p in probs]) for key in ('idx', 'npos', 'pair_a', 'pair_b', 'sizes'))
+        off = np.concatenate([[0], np.cumsum(sizes)])
+        est_off = np.concatenate([[0], np.cumsum([len(p['npos']) for p in probs])])
+        cb = np.concatenate([_ovo.bounds(est.C, p) for p in probs])
         # ---- the device: nothing below loops over estimators
         dev = LA.device()
-        solver = SVC(kernel=est.kernel)                      # carrier of the kernel-matrix code of SVC (kernel and gamma only)
-        solver._gamma = gamma
         Xd = torch.from_numpy(X).to(dev)
         G = LA.dgemm(Xd, Xd, tb=True)
-        if est.kernel == 'rbf':
-            sq = torch.diagonal(G).contiguous()              # |x_i|^2: the Gram diagonal (libsvm: dot(x_i, x_i))
-            K = torch.empty_like(G)
-            call('xps_rbf_from_gram_f64', G.data_ptr(), G.stride(0), sq.data_ptr(), sq.data_ptr(), n, n, float(gamma), K.data_ptr(),
-                 K.stride(0), stream())
-        else:
-            sq, K = None, G
-        ints = np.concatenate([idx, off, npos, pair_a, pair_b, est_off]).astype(np.int32)       # one upload of all index lists
-        ints_d = torch.from_numpy(ints).to(dev)
-        cuts = np.cumsum([0, len(idx), len(off), Q, Q, Q, E + 1])
-        idx_d, off_d, npos_d, pa_d, pb_d, eo_d = (ints_d[a:b] for a, b in zip(cuts[:-1], cuts[1:]))
-        cb_d = torch.from_numpy(cb).to(dev)
-        alpha = torch.empty(len(idx), dtype=torch.float64, device=dev)
-        rho = torch.empty(Q, dtype=torch.float64, device=dev)
-        iters = torch.empty(Q, dtype=torch.int32, device=dev)
-        call('xps_svm_smo_f64', K.data_ptr(), K.stride(0), idx_d.data_ptr(), off_d.data_ptr(), npos_d.data_ptr(), Q, max_pts,
-             cb_d.data_ptr(), float(est.tol), max_iter, alpha.data_ptr(), rho.data_ptr(), iters.data_ptr(), stream())
-        coef = torch.empty(Q, n, dtype=torch.float64, device=dev)
-        call('xps_bag_coef_scatter_f64', alpha.data_ptr(), idx_d.data_ptr(), off_d.data_ptr(), npos_d.data_ptr(), Q, n, coef.data_ptr(),
-             coef.stride(0), stream())
+        sq = torch.diagonal(G).contiguous() if est.kernel == 'rbf' else None           # |x_i|^2: the Gram diagonal (libsvm: dot(x_i, x_i))
+        K = _ovo.kernel_from_gram(est.kernel, gamma, G, sq, sq)
+        idx_d, off_d, npos_d, pa_d, pb_d, eo_d = _ovo.upload_int32([idx, off, npos, pair_a, pair_b, est_off], dev)
+        alpha, rho, iters = _ovo.smo(K, idx_d, off_d, npos_d, int(sizes.max()), cb, est.tol, est.max_iter)
+        coef = _ovo.coef_scatter(alpha, idx_d, off_d, npos_d, n)
         if est.kernel == 'linear':
             self._W, self._coef = LA.dgemm(coef, Xd), None  # (Q, d) weight vectors; the coefficients are not needed again
             self._Xd = None
         else:
             self._W, self._coef = None, coef
             self._Xd = Xd
-        self._solver, self._sq, self._rho = solver, sq, rho
-        self._ints = ints_d                                  # (the views below share its storage)
-        self._pair_a, self._pair_b, self._est_off = pa_d, pb_d, eo_d
-        self._Q, self._E = Q, E
-        self._samples = samples
+        self._kernel, self._gamma, self._sq, self._rho = est.kernel, gamma, sq, rho
+        self._pair_a, self._pair_b, self._est_off = pa_d, pb_d, eo_d        # (views of the one int32 upload)
+        self._E, self._samples = E, samples
         self.classes_ = classes
         self.n_classes_ = k
         self.n_features_in_ = d
@@ -229,7 +185,7 @@ class BaggingClassifier(ClassifierMixin, BaseEstimator):
         Xd = torch.from_numpy(X).to(LA.device())
         if self._W is not None:
             return LA.dgemm(Xd, self._W, tb=True)
-        Kx = self._solver._kernel_matrix(Xd, SVC._row_sq_norms(Xd), self._Xd, self._sq)            # (m, n)
+        Kx = _ovo.kernel_matrix(self._kernel, self._gamma, Xd, _ovo.row_sq_norms(Xd), self._Xd, self._sq)      # (m, n)
         return LA.dgemm(Kx, self._coef, tb=True)
 
     def _pair_decisions(self, X):

@@ -17,7 +17,8 @@ per chunk    (all models = (candidate, fold) pairs whose kernel matrices fit ``m
 
 Scores, ranks and ``cv_results_`` are assembled on the host from the confusion tables.  The per-fold rules are ``SVC.fit``'s
 applied to the fold's training rows (``gamma='scale'``, ``class_weight='balanced'``, class members in original order, libsvm's pair
-order, fewer pairs for a fold that lost a class).  There is no CPU fallback."""
+order, fewer pairs for a fold that lost a class), posed by the builder ``SVC.fit`` uses and solved by the same driver
+(decoders/_ovo.py).  There is no CPU fallback."""
 import numpy as np
 import torch
 from scipy.stats import rankdata
@@ -28,7 +29,8 @@ from sklearn.pipeline import Pipeline
 from .._dev import stream
 from .._lib import call, lib
 from ..alignment import _linalg as LA
-from .svm import SVC, _class_weights
+from . import _ovo
+from .svm import SVC
 
 BATCHED = ('C', 'gamma')                    # the SVC parameters that are batched on the device; every other key is an outer key
 SCORINGS = (None, 'accuracy', 'balanced_accuracy')
@@ -89,33 +91,7 @@ def _same_outer(a, b):
         return False
 
 
-# ------------------------------------------------------------------------------------------------ problems (host)
-def fold_problems(yi_train, positions, classes, class_weight):
-    """The class-pair problems ``SVC.fit`` would build on the training rows of one fold.  ``yi_train``: their class indices into
-    ``classes`` (all classes of y), in the order of ``X[train]``; ``positions``: the view row of each.  Returns ``idx`` (view rows,
-    problem after problem), ``sizes``, ``npos``, ``pair_a`` / ``pair_b`` (indices into ``classes``) and ``weight`` (per point: the
-    class weight computed from THIS fold's labels; the bound is C * weight).  A class the fold lost takes its pairs with it; a fold
-    left with one class raises sklearn's ``ValueError``."""
-    yi_train = np.asarray(yi_train)
-    positions = np.asarray(positions)
-    present = np.flatnonzero(np.bincount(yi_train, minlength=len(classes)))
-    if len(present) < 2:
-        raise ValueError(f'The number of classes has to be greater than one; got {len(present)} class')
-    cw = _class_weights(class_weight, np.asarray(classes)[present], np.searchsorted(present, yi_train))
-    members = [positions[yi_train == c].astype(np.int32) for c in present]          # original order inside a class
-    idx, weight, sizes, npos, pair_a, pair_b = [], [], [], [], [], []
-    for i, a in enumerate(present):
-        for j in range(i + 1, len(present)):
-            idx += [members[i], members[j]]
-            weight += [np.full(len(members[i]), cw[i]), np.full(len(members[j]), cw[j])]
-            sizes.append(len(members[i]) + len(members[j]))
-            npos.append(len(members[i]))
-            pair_a.append(int(a))
-            pair_b.append(int(present[j]))
-    return dict(idx=np.concatenate(idx), weight=np.concatenate(weight), sizes=np.asarray(sizes, dtype=np.int64),
-                npos=np.asarray(npos, dtype=np.int32), pair_a=np.asarray(pair_a, dtype=np.int32), pair_b=np.asarray(pair_b, dtype=np.int32))
-
-
+# ------------------------------------------------------------------------------------------------ the plan (host)
 class Plan:
     """Host description of a search: ``views`` (feature matrices), ``matrices`` ((view, gamma value) per kernel matrix, the matrices
     of a view adjacent) and ``models`` (one dict per (candidate, fold): cand, fold, matrix, C, problems, test_pos, ytest)."""
@@ -143,13 +119,15 @@ def build_plan(estimator, split_candidates, X, yi, classes, splits):
     gamma_cache = {}
 
     def add_models(view, fold, cands, Ztr, train_pos, test_pos, tr, te):
-        problems = fold_problems(yi[tr], train_pos, classes, svc.class_weight)
+        cls, yi_tr = np.unique(yi[tr], return_inverse=True)   # SVC.fit's rules on THIS fold's rows: its classes, its 'balanced' weights
+        problems = _ovo.pair_problems(yi_tr, train_pos, _ovo.class_weights(svc.class_weight, classes[cls], yi_tr))
+        problems['pair_a'], problems['pair_b'] = (cls[problems[key]].astype(np.int32) for key in ('pair_a', 'pair_b'))
         for c in cands:
             batched = split_candidates[c][0]
             spec = batched.get('gamma', svc.gamma)
             key = (view, fold, spec if isinstance(spec, str) else float(spec))
             if key not in gamma_cache:                          # SVC.fit's rule on the features handed to THIS fold's fit
-                gamma_cache[key] = SVC(kernel=svc.kernel, gamma=spec)._gamma_value(Ztr)
+                gamma_cache[key] = _ovo.gamma_value(svc.kernel, spec, Ztr)
             plan.models.append(dict(cand=c, fold=fold, matrix=plan.matrix(view, gamma_cache[key]), C=float(batched.get('C', svc.C)),
                                     problems=problems, test_pos=np.asarray(test_pos, dtype=np.int32), ytest=yi[te].astype(np.int32)))
 
@@ -252,6 +230,10 @@ def assemble_results(candidates, scores):
 
 
 # ------------------------------------------------------------------------------------------------ the device
+def _cat(dicts, key):
+    return np.concatenate([d[key] for d in dicts])
+
+
 def _run_chunk(plan, mats, kernel, tol, svc_max_iter, k):
     """Kernel matrices ``mats`` (adjacent per view) and all their models: per view an upload, a Gram product and, for rbf, one
     multi-gamma launch; then one SMO launch, one scoring launch and one download.  Returns (models, conf (S, k, k), pred, tst_off)."""
@@ -270,7 +252,7 @@ def _run_chunk(plan, mats, kernel, tol, svc_max_iter, k):
         n = Zd.shape[0]
         G = LA.dgemm(Zd, Zd, tb=True)
         if kernel == 'rbf':
-            sq = SVC._row_sq_norms(Zd)
+            sq = _ovo.row_sq_norms(Zd)
             gammas = torch.tensor([plan.matrices[m][1] for m in mats[i:j]], dtype=torch.float64).to(dev)
             call('xps_rbf_multi_from_gram_f64', G.data_ptr(), G.stride(0), sq.data_ptr(), sq.data_ptr(), n, n, gammas.data_ptr(), j - i,
                  Kbuf.data_ptr() + 8 * int(base[i]), n, n * n, stream())
@@ -280,32 +262,24 @@ def _run_chunk(plan, mats, kernel, tol, svc_max_iter, k):
     models = [mod for mod in plan.models if mod['matrix'] in slot]
     models.sort(key=lambda mod: slot[mod['matrix']])            # (stable: plan order inside a matrix)
     S = len(models)
-    nprob = np.array([len(mod['problems']['npos']) for mod in models], dtype=np.int64)
+    probs = [mod['problems'] for mod in models]
+    nprob = np.array([len(p['npos']) for p in probs], dtype=np.int64)
     mn = np.array([plan.views[plan.matrices[mod['matrix']][0]].shape[0] for mod in models], dtype=np.int64)
     mbase = np.array([base[slot[mod['matrix']]] for mod in models], dtype=np.int64)
-    sizes_q = np.concatenate([mod['problems']['sizes'] for mod in models])
+    sizes_q = _cat(probs, 'sizes')
     off = np.concatenate([[0], np.cumsum(sizes_q)])
     tst_off = np.concatenate([[0], np.cumsum([len(mod['test_pos']) for mod in models])])
     mod_off = np.concatenate([[0], np.cumsum(nprob)])
     if max(off[-1], tst_off[-1]) > np.iinfo(np.int32).max:
         raise ValueError('the chunk holds more training points than int32 offsets address: lower max_kernel_bytes')
     Q, T = int(mod_off[-1]), int(tst_off[-1])
-    max_pts = int(sizes_q.max())
-    ints = [np.concatenate([mod['problems']['idx'] for mod in models]), off, np.concatenate([mod['problems']['npos'] for mod in models]),
-            np.concatenate([mod['problems']['pair_a'] for mod in models]), np.concatenate([mod['problems']['pair_b'] for mod in models]),
-            np.concatenate([mod['test_pos'] for mod in models]), np.concatenate([mod['ytest'] for mod in models]), mn]
-    cuts = np.cumsum([0] + [len(a) for a in ints])
-    ints_d = torch.from_numpy(np.concatenate(ints).astype(np.int32)).to(dev)                    # one upload of all index lists
-    idx_d, off_d, npos_d, pa_d, pb_d, tst_d, yt_d, mn_d = (ints_d[a:b] for a, b in zip(cuts[:-1], cuts[1:]))
+    idx_d, off_d, npos_d, pa_d, pb_d, tst_d, yt_d, mn_d = _ovo.upload_int32(
+        [_cat(probs, 'idx'), off, _cat(probs, 'npos'), _cat(probs, 'pair_a'), _cat(probs, 'pair_b'), _cat(models, 'test_pos'),
+         _cat(models, 'ytest'), mn], dev)
     longs_d = torch.from_numpy(np.concatenate([np.repeat(mbase, nprob), np.repeat(mn, nprob), mbase, mn])).to(dev)
     kbase_d, kld_d, mbase_d, mld_d = longs_d[:Q], longs_d[Q:2 * Q], longs_d[2 * Q:2 * Q + S], longs_d[2 * Q + S:]
-    cb_d = torch.from_numpy(np.concatenate([mod['C'] * mod['problems']['weight'] for mod in models])).to(dev)
-    alpha = torch.empty(int(off[-1]), dtype=torch.float64, device=dev)
-    rho = torch.empty(Q, dtype=torch.float64, device=dev)
-    iters = torch.empty(Q, dtype=torch.int32, device=dev)
-    max_iter = int(svc_max_iter) if svc_max_iter and svc_max_iter > 0 else max(10_000_000, 100 * max_pts)
-    call('xps_svm_smo_multi_f64', Kbuf.data_ptr(), kbase_d.data_ptr(), kld_d.data_ptr(), idx_d.data_ptr(), off_d.data_ptr(), npos_d.data_ptr(),
-         Q, max_pts, cb_d.data_ptr(), float(tol), max_iter, alpha.data_ptr(), rho.data_ptr(), iters.data_ptr(), stream())
+    cb = np.concatenate([_ovo.bounds(mod['C'], mod['problems']) for mod in models])
+    alpha, rho, _ = _ovo.smo(Kbuf, idx_d, off_d, npos_d, int(sizes_q.max()), cb, tol, svc_max_iter, kbase_d, kld_d)
     out = torch.empty(S * k * k + max(T, 1), dtype=torch.int32, device=dev)                     # conf, then pred: one download
     ws_bytes = int(lib().xps_svm_cv_score_f64_workspace(S))
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
@@ -377,10 +351,6 @@ class SVCSearchCV(BaseEstimator):
         if not splits:
             raise ValueError('cv yields no split')
         plan = build_plan(self.estimator, split_candidates, X, yi, classes, splits)
-        limit = int(lib().xps_svm_smo_f64_max_points())
-        max_pts = max(int(mod['problems']['sizes'].max()) for mod in plan.models)
-        if max_pts > limit:
-            raise ValueError(f'a class pair has {max_pts} samples; the LDS-resident solver takes {limit}')
         # ---- the device: no loop over candidates or folds below, only over views (uploads) and chunks
         conf = np.zeros((len(candidates), len(splits), k, k), dtype=np.int32)
         labels = [np.empty((len(candidates), len(te)), dtype=classes.dtype) for _, te in splits]

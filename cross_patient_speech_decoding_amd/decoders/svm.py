@@ -10,14 +10,15 @@ libsvm solves: one C-SVC per class pair (classes ascending, the lower class posi
 tolerance ``tol`` on the maximal KKT violation, libsvm's ``rho``; per-point upper bound C * class_weight * sample_weight; the
 prediction is libsvm's one-vs-one vote (ties: the lowest class).  On the device: the Gram matrix X X^T (f64 MFMA), for
 ``kernel='rbf'`` exp(-gamma ||x - y||^2) from it (csrc/xps_svm.hip, libsvm's formula), ALL pair problems in one launch, the
-decision values as f64 GEMMs.  There is no CPU fallback."""
+decision values as f64 GEMMs.  What a fit resolves from its data, how it poses the pair problems and how it launches them is
+shared with the bagged ensemble and the grid search: decoders/_ovo.py.  There is no CPU fallback."""
 import numpy as np
 import torch
 from sklearn.base import BaseEstimator, ClassifierMixin
 
-from .._dev import stream
-from .._lib import call, lib
 from ..alignment import _linalg as LA
+from . import _ovo
+from ._ovo import class_weights as _class_weights  # noqa: F401  (imported from here by the tests)
 
 
 def _ovr_from_ovo(dec, n_classes):
@@ -36,17 +37,6 @@ def _ovr_from_ovo(dec, n_classes):
             votes[predictions[:, k] == 1, j] += 1
             k += 1
     return votes + sums / (3 * (np.abs(sums) + 1))
-
-
-def _class_weights(class_weight, classes, yi):
-    """sklearn.utils.class_weight.compute_class_weight on the y handed to fit (``yi``: its class indices)."""
-    if class_weight is None:
-        return np.ones(len(classes))
-    if isinstance(class_weight, str):
-        if class_weight != 'balanced':
-            raise ValueError("class_weight must be 'balanced', a dict or None")
-        return len(yi) / (len(classes) * np.bincount(yi, minlength=len(classes)).astype(np.float64))
-    return np.array([float(class_weight.get(c, 1.0)) for c in classes])
 
 
 class SVC(ClassifierMixin, BaseEstimator):
@@ -73,35 +63,8 @@ class SVC(ClassifierMixin, BaseEstimator):
         if self.decision_function_shape not in ('ovr', 'ovo'):
             raise ValueError("decision_function_shape must be 'ovr' or 'ovo'")
 
-    # ------------------------------------------------------------------ kernels
     def _gamma_value(self, X):
-        if self.kernel != 'rbf':
-            return 0.0
-        if isinstance(self.gamma, str):
-            if self.gamma == 'scale':                       # sklearn: 1 / (n_features * X.var()) of the X handed to fit
-                var = float(X.var())
-                return 1.0 / (X.shape[1] * var) if var != 0 else 1.0
-            if self.gamma == 'auto':
-                return 1.0 / X.shape[1]
-            raise ValueError(f"When 'gamma' is a string, it should be either 'scale' or 'auto'. Got '{self.gamma}' instead.")
-        if self.gamma < 0:
-            raise ValueError('gamma must be non-negative')
-        return float(self.gamma)
-
-    @staticmethod
-    def _row_sq_norms(Ad, chunk=2048):
-        """|a_i|^2 as the diagonal of the Gram matrix of the rows (f64 MFMA GEMM, in chunks of rows; no element-wise host math)."""
-        return torch.cat([torch.diagonal(LA.dgemm(Ad[i:i + chunk], Ad[i:i + chunk], tb=True)) for i in range(0, Ad.shape[0], chunk)]).contiguous()
-
-    def _kernel_matrix(self, Ad, na, Bd, nb):
-        """K(A, B) on the device: Gram matrix by the f64 MFMA GEMM; rbf: exp(-gamma (|a|^2 + |b|^2 - 2 a.b)) from it."""
-        G = LA.dgemm(Ad, Bd, tb=True)
-        if self.kernel == 'linear':
-            return G
-        K = torch.empty_like(G)
-        call('xps_rbf_from_gram_f64', G.data_ptr(), G.stride(0), na.data_ptr(), nb.data_ptr(), G.shape[0], G.shape[1], float(self._gamma),
-             K.data_ptr(), K.stride(0), stream())
-        return K
+        return _ovo.gamma_value(self.kernel, self.gamma, X)
 
     # ------------------------------------------------------------------ fit
     def fit(self, X, y, sample_weight=None):
@@ -112,7 +75,7 @@ class SVC(ClassifierMixin, BaseEstimator):
             raise ValueError('X must be (n_samples, n_features) and y (n_samples,)')
         self._gamma = self._gamma_value(X)
         classes, yi_all = np.unique(y, return_inverse=True)
-        cw = _class_weights(self.class_weight, classes, yi_all)
+        cw = _ovo.class_weights(self.class_weight, classes, yi_all)
         self.class_weight_ = cw
         # sample weights (BaggingClassifier passes the bootstrap multiplicities): per-point bound C * class weight * w; zero-weight
         # points are dropped before training, as sklearn's libsvm does
@@ -125,46 +88,19 @@ class SVC(ClassifierMixin, BaseEstimator):
         if len(self.classes_) != len(classes):               # a class lost all its weight: its weight entry goes with it
             cw = cw[np.isin(classes, self.classes_)]
         k = len(self.classes_)
-        if k < 2:
-            raise ValueError('The number of classes has to be greater than one; got 1 class')
         n = X.shape[0]
-        members = [np.flatnonzero(yi == c).astype(np.int32) for c in range(k)]       # original order inside a class (libsvm groups so)
-        idx, off, npos, pairs = [], [0], [], []
-        for a in range(k):
-            for b in range(a + 1, k):
-                idx += [members[a], members[b]]
-                off.append(off[-1] + len(members[a]) + len(members[b]))
-                npos.append(len(members[a]))
-                pairs.append((a, b))
-        idx = np.concatenate(idx)
-        max_pts = int(max(np.diff(off)))
-        if max_pts > lib().xps_svm_smo_f64_max_points():
-            raise ValueError(f'a class pair has {max_pts} samples; the LDS-resident solver takes {lib().xps_svm_smo_f64_max_points()}')
+        p = _ovo.pair_problems(yi, np.arange(n), cw, w)
+        off = np.concatenate([[0], np.cumsum(p['sizes'])])
         dev = LA.device()
         Xd = torch.from_numpy(X).to(dev)
-        self._sq = self._row_sq_norms(Xd) if self.kernel == 'rbf' else None
-        K = self._kernel_matrix(Xd, self._sq, Xd, self._sq)
-        idx_d = torch.from_numpy(idx).to(dev)
-        off_d = torch.tensor(off, dtype=torch.int32, device=dev)
-        npos_d = torch.tensor(npos, dtype=torch.int32, device=dev)
-        P = len(pairs)
-        alpha = torch.empty(len(idx), dtype=torch.float64, device=dev)
-        rho = torch.empty(P, dtype=torch.float64, device=dev)
-        iters = torch.empty(P, dtype=torch.int32, device=dev)
-        max_iter = int(self.max_iter) if self.max_iter and self.max_iter > 0 else max(10_000_000, 100 * max_pts)
-        cb = torch.from_numpy(float(self.C) * cw[yi[idx]] * w[idx]).to(dev)
-        call('xps_svm_smo_f64', K.data_ptr(), K.stride(0), idx_d.data_ptr(), off_d.data_ptr(), npos_d.data_ptr(), P, max_pts,
-             cb.data_ptr(), float(self.tol), max_iter, alpha.data_ptr(), rho.data_ptr(), iters.data_ptr(), stream())
-        # signed dual coefficients of every pair scattered into a dense (P, n) matrix
-        coef = torch.zeros(P, n, dtype=torch.float64, device=dev)
-        sign = torch.ones(len(idx), dtype=torch.float64, device=dev)
-        for p_, (o0, o1, npp) in enumerate(zip(off[:-1], off[1:], npos)):
-            sign[o0 + npp:o1] = -1.0
-        rows = torch.repeat_interleave(torch.arange(P, device=dev), torch.from_numpy(np.diff(off)).to(dev))
-        coef[rows, idx_d.long()] = alpha * sign
+        self._sq = _ovo.row_sq_norms(Xd) if self.kernel == 'rbf' else None
+        K = _ovo.kernel_matrix(self.kernel, self._gamma, Xd, self._sq, Xd, self._sq)
+        idx_d, off_d, npos_d = _ovo.upload_int32([p['idx'], off, p['npos']], dev)
+        alpha, rho, iters = _ovo.smo(K, idx_d, off_d, npos_d, int(p['sizes'].max()), _ovo.bounds(self.C, p), self.tol, self.max_iter)
+        coef = _ovo.coef_scatter(alpha, idx_d, off_d, npos_d, n)    # signed dual coefficients of every pair, dense (P, n)
         self._Xd = Xd
         self._rho = rho
-        self._pairs = pairs
+        self._pairs = list(zip(p['pair_a'].tolist(), p['pair_b'].tolist()))
         self.n_iter_ = iters.cpu().numpy()
         self.dual_coef_pairs_ = coef                                # (kept on the device; sklearn's dual_coef_ packs it differently)
         self.n_features_in_ = X.shape[1]
@@ -181,7 +117,7 @@ class SVC(ClassifierMixin, BaseEstimator):
         Xd = torch.from_numpy(X).to(LA.device())
         if self.kernel == 'linear':
             return (LA.dgemm(Xd, self._W, tb=True) - self._rho[None, :]).cpu().numpy()     # (m, P)
-        Kx = self._kernel_matrix(Xd, self._row_sq_norms(Xd), self._Xd, self._sq)                     # (m, n)
+        Kx = _ovo.kernel_matrix(self.kernel, self._gamma, Xd, _ovo.row_sq_norms(Xd), self._Xd, self._sq)      # (m, n)
         return (LA.dgemm(Kx, self.dual_coef_pairs_, tb=True) - self._rho[None, :]).cpu().numpy()
 
     def decision_function(self, X):

@@ -306,6 +306,24 @@ def test_estimators_that_lost_a_class_have_fewer_pairs():
         BaggingClassifier(DeviceSVC(kernel='linear'), n_estimators=70, max_samples=2, random_state=0).fit(X, y)
 
 
+def test_estimators_that_see_every_row_pose_the_single_svcs_problems():
+    """bootstrap=False, max_samples=1.0: every estimator is handed every row with weight 1, so each poses the problems of the
+    single SVC on the same kernel matrix, and the one-workgroup SMO takes the same steps: iterations, rho and the pair decisions
+    are the single SVC's bit for bit."""
+    from cross_patient_speech_decoding_amd.decoders import SVC as DeviceSVC
+    from cross_patient_speech_decoding_amd.decoders import BaggingClassifier
+    X, y, Xte, _, _ = linear_data(64, 6, 3)
+    svc = DeviceSVC(kernel='linear').fit(X, y)
+    bag = BaggingClassifier(DeviceSVC(kernel='linear'), n_estimators=2, bootstrap=False, max_samples=1.0).fit(X, y)
+    rho, P = bag._rho.cpu().numpy(), len(svc.n_iter_)
+    assert P == 3 and rho.shape == (2 * P,) and (svc.n_iter_ > 0).all()
+    dec, dec_svc = bag._pair_decisions(Xte), svc._pair_decisions(Xte)
+    for e in range(2):
+        np.testing.assert_array_equal(bag.n_iter_[e], svc.n_iter_)
+        np.testing.assert_array_equal(rho[e * P:(e + 1) * P].view(np.int64), svc._rho.cpu().numpy().view(np.int64))
+        np.testing.assert_array_equal(dec[:, e * P:(e + 1) * P].view(np.int64), dec_svc.view(np.int64))
+
+
 # ------------------------------------------------------------------------------------------------ 5. one launch per fit
 def test_one_smo_launch_one_scatter_launch_per_fit_one_vote_launch_per_predict(monkeypatch):
     from collections import Counter
