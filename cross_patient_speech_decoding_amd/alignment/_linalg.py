@@ -567,3 +567,197 @@ def pinv_small(M):
     cutoff = 1e-15 * (s.max() if len(s) else 0.0)
     inv = np.where(s > cutoff, 1.0 / np.where(s > cutoff, s, 1.0), 0.0)
     return dgemm(to_device(Vt.T * inv), to_device(U), tb=True).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------ fold-batched tables
+# The grouped kernels (csrc/xps_fold_align.hip) read device tables of int64 words and trust them: every extent is checked
+# here, against the tensors themselves, before a table is uploaded.
+XCOV_WORDS, APPLY_WORDS, CNDAVG_WORDS = 20, 12, 8             # XPS_*_WORDS of include/xps.h
+XCOV_SPLIT_ROWS, XCOV_MAX_SPLITS = 256, 64
+
+
+def xcov_grouped_splits(rows):
+    """K splits of a grouped cross-moment problem of `rows` rows: one per 256 rows, at most 64 (so more than 256 rows take
+    the split-K route).  A function of the problem's own shape alone: a problem gives the same bits in any table."""
+    return int(max(1, min(XCOV_MAX_SPLITS, -(-int(rows) // XCOV_SPLIT_ROWS))))
+
+
+def _check_matrix(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 and t.dtype in (torch.float32, F64)
+            and (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1]):
+        raise ValueError(f'{what}: a 2-D float32 / float64 device matrix with contiguous rows is needed')
+
+
+def _check_vector(v, n, what):
+    if v is None:
+        return 0
+    if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == F64 and v.dim() == 1 and v.is_contiguous()
+            and v.shape[0] == n):
+        raise ValueError(f'{what}: a contiguous float64 device vector of {n} elements is needed')
+    return v.data_ptr()
+
+
+def xcov_grouped(problems):
+    """problems: list of (A, B, blk_a, blk_b, blk_len, c_a, c_b): A (n_a, da) and B (n_b, db) device matrices (float32 or
+    float64), blk_a / blk_b integer sequences of equal length (first row of each block), c_a / c_b float64 device vectors or
+    None.  One xps_xcov_grouped_f64 call.  Returns (out, offsets): `out` a flat float64 device tensor, problem i at
+    out[offsets[i]:offsets[i + 1]] as [C (da x db) | s_a | s_b | count]."""
+    dev = device()
+    n = len(problems)
+    tab = np.zeros((n, XCOV_WORDS), dtype=np.int64)
+    offs = np.zeros(n + 1, dtype=np.int64)
+    blks, tiles, nblk_tot, slab_tot = [], [], 0, 0
+    for i, (A, B, ba, bb, blk_len, ca, cb) in enumerate(problems):
+        _check_matrix(A, 'xcov_grouped A')
+        _check_matrix(B, 'xcov_grouped B')
+        ba, bb = np.asarray(ba, dtype=np.int64).reshape(-1), np.asarray(bb, dtype=np.int64).reshape(-1)
+        blk_len = int(blk_len)
+        if len(ba) != len(bb) or blk_len < 1:
+            raise ValueError('xcov_grouped: the two block lists differ in length, or blk_len < 1')
+        if len(ba) and (ba.min() < 0 or bb.min() < 0 or ba.max() + blk_len > A.shape[0] or bb.max() + blk_len > B.shape[0]):
+            raise ValueError('xcov_grouped: a row block reaches outside its matrix')
+        da, db = A.shape[1], B.shape[1]
+        rows = len(ba) * blk_len
+        if rows >= 2 ** 31:
+            raise ValueError('xcov_grouped: row count must fit in int32')
+        splits = xcov_grouped_splits(rows)
+        kchunk = -(-max(-(-rows // splits), 1) // 16) * 16
+        ln = da * db + da + db
+        tab[i] = [A.data_ptr(), B.data_ptr(), A.stride(0), B.stride(0), _is32(A), _is32(B),
+                  _check_vector(ca, da, 'xcov_grouped c_a'), _check_vector(cb, db, 'xcov_grouped c_b'),
+                  nblk_tot, nblk_tot + len(ba), len(ba), blk_len, da, db, offs[i], slab_tot, splits, kchunk, 0, 0]
+        offs[i + 1] = offs[i] + ln + 1
+        blks += [ba, bb]
+        nblk_tot += 2 * len(ba)
+        slab_tot += splits * ln
+        mt, nt = -(-da // 64), -(-db // 64)
+        t = np.empty((mt, nt, splits, 4), dtype=np.int32)
+        t[..., 0] = i
+        t[..., 1] = np.arange(mt)[:, None, None]
+        t[..., 2] = np.arange(nt)[None, :, None]
+        t[..., 3] = np.arange(splits)[None, None, :]
+        tiles.append(t.reshape(-1, 4))
+    out = torch.empty(int(offs[-1]), dtype=F64, device=dev)
+    if n == 0:
+        return out, offs
+    slabs = torch.empty(max(slab_tot, 1), dtype=F64, device=dev)
+    words = torch.empty(n * XCOV_WORDS + max(nblk_tot, 1), dtype=torch.int64, device=dev)
+    base = words.data_ptr() + 8 * n * XCOV_WORDS
+    tab[:, 8] = base + 8 * tab[:, 8]
+    tab[:, 9] = base + 8 * tab[:, 9]
+    tab[:, 14] = out.data_ptr() + 8 * tab[:, 14]
+    tab[:, 15] = slabs.data_ptr() + 8 * tab[:, 15]
+    host = np.concatenate([tab.reshape(-1)] + blks + ([np.zeros(1, dtype=np.int64)] if nblk_tot == 0 else []))
+    words.copy_(torch.from_numpy(host))
+    tiles = np.ascontiguousarray(np.concatenate(tiles))
+    tiles_d = torch.from_numpy(tiles).to(dev)
+    call('xps_xcov_grouped_f64', words.data_ptr(), n, tiles_d.data_ptr(), len(tiles),
+         int((offs[1:] - offs[:-1]).max()), stream())
+    return out, offs
+
+
+def loo_sum(inp, n_out):
+    """inp (G, len) float64 device -> (n_out, len): out[f] = sum of inp[g] over g != f in ascending g (plain adds from 0)."""
+    if not (inp.is_cuda and inp.dtype == F64 and inp.dim() == 2 and inp.is_contiguous() and 0 <= n_out <= inp.shape[0]):
+        raise ValueError('loo_sum: a contiguous (G, len) float64 device tensor and n_out <= G are needed')
+    out = torch.empty(n_out, inp.shape[1], dtype=F64, device=inp.device)
+    call('xps_loo_sum_f64', inp.data_ptr(), out.data_ptr(), inp.shape[0], n_out, inp.shape[1], stream())
+    return out
+
+
+def apply_grouped(entries):
+    """entries: list of (X, mean, W, out): out[:] = (X - mean) @ W for every entry in ONE launch.  X (rows, d_in) float32 /
+    float64, mean a float64 vector or None, W (d_in, d_out) float64, out (rows, d_out) float32 / float64 -- device matrices
+    with contiguous rows (slices of larger tensors are fine: each is addressed by its own pointer and row stride)."""
+    n = len(entries)
+    if n == 0:
+        return
+    tab = np.zeros((n, APPLY_WORDS), dtype=np.int64)
+    tiles = []
+    for i, (X, mean, W, out) in enumerate(entries):
+        for t, what in ((X, 'X'), (W, 'W'), (out, 'out')):
+            _check_matrix(t, 'apply_grouped ' + what)
+        rows, d_in = X.shape
+        d_out = W.shape[1]
+        if W.dtype != F64 or W.shape[0] != d_in or tuple(out.shape) != (rows, d_out) or rows >= 2 ** 31:
+            raise ValueError('apply_grouped: shapes of X, W and out do not fit together (W must be float64)')
+        tab[i] = [X.data_ptr(), _is32(X), X.stride(0), rows, _check_vector(mean, d_in, 'apply_grouped mean'), W.data_ptr(),
+                  W.stride(0), d_in, d_out, out.data_ptr(), out.stride(0), _is32(out)]
+        mt, nt = -(-rows // 64), -(-d_out // 64)
+        t = np.empty((mt, nt, 3), dtype=np.int32)
+        t[..., 0] = i
+        t[..., 1] = np.arange(mt)[:, None]
+        t[..., 2] = np.arange(nt)[None, :]
+        tiles.append(t.reshape(-1, 3))
+    dev = device()
+    tiles = np.ascontiguousarray(np.concatenate(tiles))
+    tab_d = torch.from_numpy(tab.reshape(-1)).to(dev)
+    tiles_d = torch.from_numpy(tiles).to(dev)
+    call('xps_apply_grouped_f64', tab_d.data_ptr(), n, tiles_d.data_ptr(), len(tiles), stream())
+
+
+def cnd_avg_folds(segments):
+    """segments: list of (src, out, trials): out[:] = mean over t in `trials` (in that order, float64 adds) of src[t].
+    src (n, ...) and out (...) contiguous float64 device tensors, trials an integer sequence.  ONE launch."""
+    n = len(segments)
+    if n == 0:
+        return
+    tab = np.zeros((n, CNDAVG_WORDS), dtype=np.int64)
+    lists, pos = [], 0
+    for i, (src, out, trials) in enumerate(segments):
+        row_len = int(np.prod(src.shape[1:]))
+        tr = np.asarray(trials, dtype=np.int64).reshape(-1)
+        if not (src.is_cuda and out.is_cuda and src.dtype == F64 and out.dtype == F64 and src.is_contiguous()
+                and out.is_contiguous() and out.numel() == row_len):
+            raise ValueError('cnd_avg_folds: contiguous float64 device tensors with out.numel() == one row of src are needed')
+        if len(tr) and (tr.min() < 0 or tr.max() >= src.shape[0]):
+            raise ValueError('cnd_avg_folds: a trial index reaches outside src')
+        tab[i, :5] = [src.data_ptr(), row_len, out.data_ptr(), pos, pos + len(tr)]
+        lists.append(tr.astype(np.int32))
+        pos += len(tr)
+    dev = device()
+    tab_d = torch.from_numpy(tab.reshape(-1)).to(dev)
+    tr_d = torch.from_numpy(np.concatenate(lists + [np.zeros(1, dtype=np.int32)])).to(dev)
+    for s0 in range(0, n, 65535):                    # (the kernel's grid limit; a fit has folds x conditions segments)
+        cnt = min(65535, n - s0)
+        call('xps_cnd_avg_folds_f64', tab_d.data_ptr() + 8 * CNDAVG_WORDS * s0, cnt, tr_d.data_ptr(),
+             int(tab[s0:s0 + cnt, 1].max()), stream())
+
+
+def eigh_psd_stack(Cs):
+    """eigh_psd of equally sized PSD matrices given as ONE (batch, n, n) float64 ndarray: one upload, one Jacobi launch, one
+    download (eigh_psd_batched uploads and shifts matrix by matrix).  Sizes beyond the one-workgroup kernel go through
+    eigh_psd_batched, which decomposes them one at a time.  Returns a list of (w descending, V)."""
+    Cs = np.ascontiguousarray(Cs, dtype=np.float64)
+    b, n, _ = Cs.shape
+    if not lib().xps_jacobi_small_supported(n, n, 0):
+        return eigh_psd_batched(list(Cs))
+    g = np.abs(Cs).sum(axis=-1).max(axis=-1)
+    sig = np.where(g > 0, g * _SHIFT, 1.0)
+    Wb = to_device(Cs + sig[:, None, None] * np.eye(n))
+    jacobi_batched(Wb, want_v=False)
+    res = [_eig_from_w(W, sg) for W, sg in zip(Wb.cpu().numpy(), sig)]
+    return [r if r is not None else eigh_psd(to_device(Cs[i])) for i, r in enumerate(res)]
+
+
+def svd_batched(Ks):
+    """Thin SVDs of equally shaped small float64 matrices given as ONE (batch, m, n) ndarray, all by one jacobi_batched
+    launch: a list of numpy (U, s, Vt) as `svd` returns.  Shapes beyond the one-workgroup kernel take `svd` one by one."""
+    Ks = np.ascontiguousarray(Ks, dtype=np.float64)
+    b, m, n = Ks.shape
+    if m < n:
+        return [(Vt.T, s, U.T) for U, s, Vt in svd_batched(np.ascontiguousarray(Ks.transpose(0, 2, 1)))]
+    if not lib().xps_jacobi_small_supported(m, n, 1):
+        return [svd(to_device(K)) for K in Ks]
+    Wb = to_device(np.ascontiguousarray(Ks.transpose(0, 2, 1)))         # [b] row j = column j of K[b]
+    Vb = jacobi_batched(Wb, want_v=True)
+    out = []
+    for W, V in zip(Wb.cpu().numpy(), Vb.cpu().numpy()):
+        s = np.linalg.norm(W, axis=1)
+        order = np.argsort(-s, kind='stable')
+        s, W, V = s[order], W[order], V[order]
+        U = np.zeros_like(W)
+        nz = s > 0
+        U[nz] = W[nz] / s[nz, None]
+        out.append((U.T, s, V))
+    return out

@@ -1,0 +1,283 @@
+// Fold-batched PCA -> CCA alignment for gfx950: every fold of a k-fold split as one device problem.
+//
+//  xps_xcov_grouped_f64    a TABLE of centred cross-moment problems in one launch (+ one reduce launch): per problem
+//                          sum (a - c_a)(b - c_b)^T, sum (a - c_a), sum (b - c_b) and the row count over two lists of
+//                          row blocks.  The tile is gemm_f64_kernel's (xps_align.hip): 64 x 64 outputs per workgroup,
+//                          16 staged rows per step, v_mfma_f64_16x16x4_f64; fp32 / fp64 inputs are converted and centred
+//                          while staged to LDS.  Split-K writes slabs that the reduce adds in slab order: two runs give
+//                          the same bits.
+//  xps_loo_sum_f64         out[f] = sum over g != f of in[g], ascending g, plain adds.
+//  xps_apply_grouped_f64   a table of (X - mean) W products with ragged widths in one launch (xps_apply_f64's arithmetic).
+//  xps_cnd_avg_folds_f64   a table of segment means: fp64 sums over listed trials in list order.
+//
+// The tables are DEVICE arrays of int64 words built by the caller (alignment/_linalg.py checks every extent against the
+// tensors it was given before it uploads one); the kernels trust them.
+//
+// f64 MFMA operand mapping (16x16x4, lane l: n = l & 15, kq = l >> 4):
+//   A[row n][k kq], B[k kq][col n], D[row = kq + 4*i][col = n] in register i.
+#include "xps_common.h"
+
+namespace {
+
+constexpr int GM = 64, GN = 64, GK = 16, GLD = 66;     // gemm_f64_kernel's tile: 2 x 16 x 66 doubles = 16.5 KiB of LDS
+
+// words of one xps_xcov_grouped_f64 problem
+enum { XP_A, XP_B, XP_LDA, XP_LDB, XP_A32, XP_B32, XP_CA, XP_CB, XP_BLKA, XP_BLKB, XP_NBLK, XP_BLKLEN, XP_DA, XP_DB,
+       XP_OUT, XP_SLAB, XP_SPLITS, XP_KCHUNK, XP_WORDS_USED };
+static_assert(XP_WORDS_USED <= XPS_XCOV_GROUPED_WORDS, "problem words");
+// words of one xps_apply_grouped_f64 entry
+enum { AP_X, AP_X32, AP_LDX, AP_ROWS, AP_MEAN, AP_W, AP_LDW, AP_DIN, AP_DOUT, AP_OUT, AP_LDO, AP_O32, AP_WORDS_USED };
+static_assert(AP_WORDS_USED <= XPS_APPLY_GROUPED_WORDS, "entry words");
+// words of one xps_cnd_avg_folds_f64 segment
+enum { CS_SRC, CS_ROWLEN, CS_OUT, CS_BEGIN, CS_END, CS_WORDS_USED };
+static_assert(CS_WORDS_USED <= XPS_CND_AVG_FOLDS_WORDS, "segment words");
+
+__device__ inline double ld64(const void* p, int is_f32, long long off) {
+    return is_f32 ? (double)reinterpret_cast<const float*>(p)[off] : reinterpret_cast<const double*>(p)[off];
+}
+
+// Stage S[k][x] = M[row(k0 + k)][x0 + x] - centre[x0 + x] for 16 rows of the problem's block list; rows at or past kend and
+// columns at or past X are zero.  Thread t: row k0 + (t >> 4), columns x0 + 4 (t & 15) .. + 3.
+__device__ inline void stage_rows(const void* M, int is_f32, long long ld, const double* centre, const long long* blk,
+                                  int blk_len, double (*S)[GLD], int x0, int X, int k0, int kend, int tid) {
+    const int k = k0 + (tid >> 4), xb = x0 + (tid & 15) * 4;
+    long long row = 0;
+    if (k < kend) row = blk[k / blk_len] + (k % blk_len);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int x = xb + i;
+        double v = 0.0;
+        if (x < X && k < kend) {
+            v = ld64(M, is_f32, row * ld + x);
+            if (centre) v -= centre[x];
+        }
+        S[tid >> 4][(tid & 15) * 4 + i] = v;
+    }
+}
+
+// One workgroup per (problem, 64-row tile of C, 64-column tile of C, K split); tiles[4 t ..] = {problem, mt, nt, split}.
+// Slab of a split: [C (da x db) | s_a (da) | s_b (db)].
+__global__ __launch_bounds__(256) void xcov_grouped_kernel(const long long* __restrict__ probs, const int* __restrict__ tiles) {
+    __shared__ __attribute__((aligned(16))) double As[GK][GLD];
+    __shared__ __attribute__((aligned(16))) double Bs[GK][GLD];
+    const int* tl = tiles + 4 * (long long)blockIdx.x;
+    const long long* P = probs + (long long)tl[0] * XPS_XCOV_GROUPED_WORDS;
+    const int mt = tl[1], nt = tl[2], split = tl[3];
+    const void* A = reinterpret_cast<const void*>(P[XP_A]);
+    const void* B = reinterpret_cast<const void*>(P[XP_B]);
+    const long long lda = P[XP_LDA], ldb = P[XP_LDB];
+    const int a32 = (int)P[XP_A32], b32 = (int)P[XP_B32];
+    const double* ca = reinterpret_cast<const double*>(P[XP_CA]);
+    const double* cb = reinterpret_cast<const double*>(P[XP_CB]);
+    const long long* blka = reinterpret_cast<const long long*>(P[XP_BLKA]);
+    const long long* blkb = reinterpret_cast<const long long*>(P[XP_BLKB]);
+    const int blk_len = (int)P[XP_BLKLEN], da = (int)P[XP_DA], db = (int)P[XP_DB];
+    const int K = (int)P[XP_NBLK] * blk_len, kchunk = (int)P[XP_KCHUNK];
+    double* slab = reinterpret_cast<double*>(P[XP_SLAB]) + (long long)split * ((long long)da * db + da + db);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 15, kq = lane >> 4;
+    const int m0 = mt * GM, n0 = nt * GN;
+    const int kbeg = split * kchunk;
+    const int kend = min(K, kbeg + kchunk);
+
+    f64x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = (f64x4){0.0, 0.0, 0.0, 0.0};
+    double colsum = 0.0;                       // wave 0: s_a of column m0 + lane (nt == 0); wave 1: s_b of n0 + lane (mt == 0)
+
+    for (int k0 = kbeg; k0 < kend; k0 += GK) {
+        stage_rows(A, a32, lda, ca, blka, blk_len, As, m0, da, k0, kend, tid);
+        stage_rows(B, b32, ldb, cb, blkb, blk_len, Bs, n0, db, k0, kend, tid);
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < GK; ks += 4) {
+            const double a = As[ks + kq][wave * 16 + n];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double b = Bs[ks + kq][j * 16 + n];
+                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
+            }
+        }
+        if (wave == 0 && nt == 0) {
+#pragma unroll
+            for (int k = 0; k < GK; ++k) colsum += As[k][lane];
+        } else if (wave == 1 && mt == 0) {
+#pragma unroll
+            for (int k = 0; k < GK; ++k) colsum += Bs[k][lane];
+        }
+        __syncthreads();
+    }
+    // D layout (f64 16x16x4): col = lane & 15, row = (lane >> 4) + 4 * i
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = m0 + wave * 16 + kq + 4 * i, col = n0 + j * 16 + n;
+            if (row < da && col < db) slab[(long long)row * db + col] = acc[j][i];
+        }
+    if (wave == 0 && nt == 0 && m0 + lane < da) slab[(long long)da * db + m0 + lane] = colsum;
+    if (wave == 1 && mt == 0 && n0 + lane < db) slab[(long long)da * db + da + n0 + lane] = colsum;
+}
+
+// out of a problem: [C | s_a | s_b | count], each element the sum of its slabs in slab order.
+__global__ void xcov_grouped_reduce(const long long* __restrict__ probs) {
+    const long long* P = probs + (long long)blockIdx.y * XPS_XCOV_GROUPED_WORDS;
+    const int da = (int)P[XP_DA], db = (int)P[XP_DB], splits = (int)P[XP_SPLITS];
+    const long long len = (long long)da * db + da + db;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx > len) return;
+    double* out = reinterpret_cast<double*>(P[XP_OUT]);
+    if (idx == len) { out[len] = (double)(P[XP_NBLK] * P[XP_BLKLEN]); return; }
+    const double* slabs = reinterpret_cast<const double*>(P[XP_SLAB]);
+    double s = 0.0;
+    for (int z = 0; z < splits; ++z) s += slabs[(long long)z * len + idx];
+    out[idx] = s;
+}
+
+__global__ void loo_sum_kernel(const double* __restrict__ in, double* __restrict__ out, int G, long long len) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= len) return;
+    const int f = blockIdx.y;
+    double s = 0.0;
+    for (int g = 0; g < G; ++g)
+        if (g != f) s += in[(long long)g * len + e];
+    out[(long long)f * len + e] = s;
+}
+
+// Stage S[k][x] = X[x0 + x][k0 + k] - mean[k0 + k] (X stored row-major, k contiguous): stage_tile<true> of xps_align.hip.
+__device__ inline void stage_x(const void* X, int is_f32, long long ld, const double* mean, double (*S)[GLD], int x0, int rows,
+                               int k0, int kend, int tid) {
+    const int x = x0 + (tid >> 2), kb = k0 + (tid & 3) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int k = kb + i;
+        double v = 0.0;
+        if (x < rows && k < kend) {
+            v = ld64(X, is_f32, (long long)x * ld + k);
+            if (mean) v -= mean[k];
+        }
+        S[(tid & 3) * 4 + i][tid >> 2] = v;
+    }
+}
+__device__ inline void stage_w(const double* W, long long ld, double (*S)[GLD], int x0, int X, int k0, int kend, int tid) {
+    const int k = k0 + (tid >> 4), xb = x0 + (tid & 15) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int x = xb + i;
+        S[tid >> 4][(tid & 15) * 4 + i] = (x < X && k < kend) ? W[(long long)k * ld + x] : 0.0;
+    }
+}
+
+// One workgroup per (entry, 64-row tile, 64-column tile); tiles[3 t ..] = {entry, mt, nt}.
+__global__ __launch_bounds__(256) void apply_grouped_kernel(const long long* __restrict__ ents, const int* __restrict__ tiles) {
+    __shared__ __attribute__((aligned(16))) double As[GK][GLD];
+    __shared__ __attribute__((aligned(16))) double Bs[GK][GLD];
+    const int* tl = tiles + 3 * (long long)blockIdx.x;
+    const long long* E = ents + (long long)tl[0] * XPS_APPLY_GROUPED_WORDS;
+    const void* X = reinterpret_cast<const void*>(E[AP_X]);
+    const int x32 = (int)E[AP_X32], rows = (int)E[AP_ROWS], d_in = (int)E[AP_DIN], d_out = (int)E[AP_DOUT];
+    const long long ldx = E[AP_LDX], ldw = E[AP_LDW], ldo = E[AP_LDO];
+    const double* mean = reinterpret_cast<const double*>(E[AP_MEAN]);
+    const double* W = reinterpret_cast<const double*>(E[AP_W]);
+    void* out = reinterpret_cast<void*>(E[AP_OUT]);
+    const int o32 = (int)E[AP_O32];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 15, kq = lane >> 4;
+    const int m0 = tl[1] * GM, n0 = tl[2] * GN;
+
+    f64x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = (f64x4){0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < d_in; k0 += GK) {
+        stage_x(X, x32, ldx, mean, As, m0, rows, k0, d_in, tid);
+        stage_w(W, ldw, Bs, n0, d_out, k0, d_in, tid);
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < GK; ks += 4) {
+            const double a = As[ks + kq][wave * 16 + n];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double b = Bs[ks + kq][j * 16 + n];
+                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = m0 + wave * 16 + kq + 4 * i, col = n0 + j * 16 + n;
+            if (row < rows && col < d_out) {
+                const long long o = (long long)row * ldo + col;
+                if (o32) reinterpret_cast<float*>(out)[o] = (float)acc[j][i];
+                else reinterpret_cast<double*>(out)[o] = acc[j][i];
+            }
+        }
+}
+
+__global__ void cnd_avg_folds_kernel(const long long* __restrict__ segs, const int* __restrict__ trials) {
+    const long long* S = segs + (long long)blockIdx.y * XPS_CND_AVG_FOLDS_WORDS;
+    const long long row_len = S[CS_ROWLEN];
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= row_len) return;
+    const double* src = reinterpret_cast<const double*>(S[CS_SRC]);
+    double* out = reinterpret_cast<double*>(S[CS_OUT]);
+    const long long b = S[CS_BEGIN], en = S[CS_END];
+    if (en <= b) { out[e] = 0.0; return; }
+    double acc = src[(long long)trials[b] * row_len + e];
+    for (long long i = b + 1; i < en; ++i) acc += src[(long long)trials[i] * row_len + e];
+    out[e] = acc / (double)(en - b);
+}
+
+}  // namespace
+
+extern "C" int xps_xcov_grouped_f64(const int64_t* problems, int n_problems, const int32_t* tiles, int n_tiles, int max_out_len,
+                                    void* stream) {
+    XPS_CHECK_ARG(n_problems >= 0 && n_tiles >= 0 && max_out_len >= 0, "bad argument");
+    if (n_problems == 0) return XPS_OK;
+    XPS_CHECK_ARG(problems && (tiles || n_tiles == 0) && max_out_len >= 4, "null table");
+    XPS_CHECK_ARG(n_problems <= 65535, "more than 65535 problems in one call");
+    if (n_tiles > 0) {
+        hipLaunchKernelGGL(xcov_grouped_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream,
+                           (const long long*)problems, (const int*)tiles);
+        XPS_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(xcov_grouped_reduce, dim3(cdiv(max_out_len, 256), n_problems), dim3(256), 0, (hipStream_t)stream,
+                       (const long long*)problems);
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}
+
+extern "C" int xps_loo_sum_f64(const double* in, double* out, int n_groups, int n_out, int64_t len, void* stream) {
+    XPS_CHECK_ARG(in && out && n_groups >= 1 && n_out >= 0 && n_out <= n_groups && len >= 0 && in != out, "bad argument");
+    if (n_out == 0 || len == 0) return XPS_OK;
+    hipLaunchKernelGGL(loo_sum_kernel, dim3(cdiv(len, 256), n_out), dim3(256), 0, (hipStream_t)stream, in, out, n_groups,
+                       (long long)len);
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}
+
+extern "C" int xps_apply_grouped_f64(const int64_t* entries, int n_entries, const int32_t* tiles, int n_tiles, void* stream) {
+    XPS_CHECK_ARG(n_entries >= 0 && n_tiles >= 0, "bad argument");
+    if (n_entries == 0 || n_tiles == 0) return XPS_OK;
+    XPS_CHECK_ARG(entries && tiles, "null table");
+    hipLaunchKernelGGL(apply_grouped_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, (const long long*)entries,
+                       (const int*)tiles);
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}
+
+extern "C" int xps_cnd_avg_folds_f64(const int64_t* segments, int n_segments, const int32_t* trials, int64_t max_row_len,
+                                     void* stream) {
+    XPS_CHECK_ARG(n_segments >= 0 && max_row_len >= 0, "bad argument");
+    if (n_segments == 0 || max_row_len == 0) return XPS_OK;
+    XPS_CHECK_ARG(segments && trials, "null table");
+    XPS_CHECK_ARG(n_segments <= 65535, "more than 65535 segments in one call");
+    hipLaunchKernelGGL(cnd_avg_folds_kernel, dim3(cdiv(max_row_len, 256), n_segments), dim3(256), 0, (hipStream_t)stream,
+                       (const long long*)segments, (const int*)trials);
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}

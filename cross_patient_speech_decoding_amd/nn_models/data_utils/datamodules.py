@@ -59,6 +59,31 @@ def process_aligner(X, y, y_align, pool_data, algner, n_components=0.95):
     return torch.Tensor(X_pool), y_pool, tar_dr
 
 
+def process_aligner_folds(X, y, y_align, pool_data, splits, n_components=0.95):
+    """``process_aligner`` (with AlignCCA's defaults) for EVERY (train, test) pair of `splits` from one fold-batched fit
+    (alignment.fit_folds: all folds as one device problem).  `splits` must be what KFold / StratifiedKFold produce
+    (alignment.fold_plan raises ValueError otherwise).  Returns one (X_pool, y_pool, projector) per fold: X_pool a float32
+    DEVICE tensor (the fold's training trials of X in `train` order, then every aligned pooled patient), y_pool by
+    ``process_aligner``'s rule on y[train] (hstack quirk included), projector with ``transform`` like the fitted target PCA."""
+    from ...alignment import fit_folds
+    if y_align is None:
+        y_align = y
+    fa = fit_folds(X, y_align, pool_data, splits, n_components=n_components)
+    yn = _np(y)
+    out = []
+    for f, (tr, _) in enumerate(fa.plan.splits):
+        ys = [yn[tr]] + [_np(yy) for _, yy, _ in pool_data]
+        try:
+            y_pool = np.hstack(ys)
+        except ValueError:
+            y_pool = np.vstack(ys)
+        y_pool = torch.Tensor(y_pool).long()
+        if y_pool.dim() > 1 and y_pool.shape[1] == 1:
+            y_pool = y_pool.squeeze(1)
+        out.append((fa.train_pool(f), y_pool, fa.projector(f)))
+    return out
+
+
 def process_aligner_sharded(X, y, y_align, pool_data, algner, n_components=0.95, group=None):
     """``process_aligner`` with the PATIENTS sharded over the ranks of ``group`` (P patients <-> P GPUs).
 
@@ -299,11 +324,18 @@ class AlignedMicroDataModule(_FoldModule):
     align_before_split = False
 
     def __init__(self, data, labels, align_labels, pool_data, algner, batch_size=128, folds=20, val_size=0.2,
-                 augmentations=None, data_path=None, save_folds=False, multiview=False, process_group=None):
+                 augmentations=None, data_path=None, save_folds=False, multiview=False, process_group=None,
+                 batched_folds=False):
         super().__init__(data, labels, batch_size, folds, val_size, augmentations, data_path, save_folds)
         self.align_labels, self.pool_data, self.algner = align_labels, pool_data, algner
         self.multiview = multiview
         self.process_group = process_group           # data parallel: the pooled patients are aligned one per rank
+        self.batched_folds = batched_folds           # every fold's PCA + CCA from one alignment.fit_folds
+        if batched_folds:
+            from ...alignment import AlignCCA
+            if not (self.align_before_split and algner is AlignCCA and not multiview and process_group is None):
+                raise ValueError('batched_folds=True needs align_before_split (AlignedMicroValDataModule), algner=AlignCCA '
+                                 '(its defaults), multiview=False and no process group')
 
     def _align(self, X, y, y_align, pool):
         if self.multiview:
@@ -319,6 +351,8 @@ class AlignedMicroDataModule(_FoldModule):
         cv = self.select_cv(self.folds)
         lab1 = self.labels.squeeze(1) if (len(self.labels.shape) > 1 and self.labels.shape[1] == 1) else self.labels
         strat = lab1 if len(lab1.shape) == 1 else lab1[:, 0]
+        if self.batched_folds:
+            return self._setup_batched(list(cv.split(self.data, strat)))
         for k, (tr, te) in enumerate(cv.split(self.data, strat)):
             trd, ted = self.data[tr], self.data[te]
             trl, tel = self.labels[tr], self.labels[te]
@@ -341,6 +375,22 @@ class AlignedMicroDataModule(_FoldModule):
                 if vd is not None:
                     vd = self._project(dim_red, vd)
             ted = self._project(dim_red, ted)
+            self._store(k, train_data=ad, train_labels=al, val_data=vd, val_labels=vl, test_data=ted, test_labels=tel)
+
+
+    def _setup_batched(self, splits):
+        """The align-before-split branch of ``setup`` with every fold's alignment taken from one fold-batched fit.  The
+        random calls keep their order: the splitter shuffles once, before its first fold, and the validation splits follow
+        fold by fold."""
+        aligned = process_aligner_folds(self.data, self.labels, self.align_labels, self.pool_data, splits)
+        for k, ((tr, te), (trd, trl, dim_red)) in enumerate(zip(splits, aligned)):
+            dev, trd = trd.device, trd.cpu()
+            tel = self.labels[te]
+            vd = vl = None
+            if self.val_size > 0:
+                trd, vd, trl, vl = self._split_val(trd, trl)
+            ad, al = self._augment(trd, trl)
+            ted = dim_red.transform_device(torch.as_tensor(_np(self.data[te])).to(dev), out_f32=True).cpu()
             self._store(k, train_data=ad, train_labels=al, val_data=vd, val_labels=vl, test_data=ted, test_labels=tel)
 
 

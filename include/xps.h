@@ -528,6 +528,37 @@ int xps_xcov_f64(const void* A, int a_is_f32, int64_t lda, const double* mean_a,
                  const void* B, int b_is_f32, int64_t ldb, const double* mean_b,
                  double* C, int64_t ldc, int64_t n, int da, int db,
                  void* workspace, size_t workspace_bytes, void* stream);
+/* Fold-batched alignment (alignment/fold_align.py): every fold of a k-fold split as one device problem.  The tables below
+ * are DEVICE arrays of int64 words that the caller builds and bounds-checks (alignment/_linalg.py); pointers are stored as
+ * integers, 0 = NULL where a word is optional.
+ *
+ * xps_xcov_grouped_f64: n_problems centred cross-moment problems in one launch plus one reduce launch, on the tile of
+ * xps_xcov_f64 (f64 MFMA, float32 / float64 inputs converted and centred while staged).  A problem reads `nblk` row blocks of
+ * `blk_len` consecutive rows from A (n x da) and from B (n x db) -- block j starts at row blk_a[j] of A and blk_b[j] of B --
+ * and writes  out = [ C (da x db, ld db) | s_a (da) | s_b (db) | count ]  with
+ *   C = sum (a - c_a)(b - c_b)^T,  s_a = sum (a - c_a),  s_b = sum (b - c_b),  count = nblk * blk_len   (zeros for nblk = 0).
+ * Words of a problem (XPS_XCOV_GROUPED_WORDS each):
+ *   0 A, 1 B, 2 lda, 3 ldb, 4 a_is_f32, 5 b_is_f32, 6 c_a (or 0), 7 c_b (or 0), 8 blk_a (int64[nblk]), 9 blk_b, 10 nblk,
+ *   11 blk_len (>= 1), 12 da, 13 db, 14 out (da*db + da + db + 1 doubles), 15 slabs (splits * (da*db + da + db) doubles of
+ *   workspace owned by this problem), 16 splits (>= 1), 17 kchunk (rows per split, a multiple of 16, splits * kchunk >= rows).
+ * tiles: int32[4 * n_tiles] = {problem, row tile, column tile, split} for EVERY 64 x 64 tile of every split of every problem.
+ * Slabs are added in split order: the result does not depend on scheduling.  max_out_len = the largest da*db + da + db + 1. */
+#define XPS_XCOV_GROUPED_WORDS 20
+int xps_xcov_grouped_f64(const int64_t* problems, int n_problems, const int32_t* tiles, int n_tiles, int max_out_len,
+                         void* stream);
+/* out[f][e] = sum over g != f, in ascending g, of in[g][e]  (f < n_out <= n_groups, e < len): plain float64 adds from 0. */
+int xps_loo_sum_f64(const double* in, double* out, int n_groups, int n_out, int64_t len, void* stream);
+/* n_entries products  out = (X - mean) W  in one launch, xps_apply_f64's arithmetic.  Words of an entry
+ * (XPS_APPLY_GROUPED_WORDS each): 0 X, 1 x_is_f32, 2 ldx, 3 rows, 4 mean (float64[d_in], or 0), 5 W (float64 d_in x d_out),
+ * 6 ldw, 7 d_in, 8 d_out, 9 out, 10 ldo, 11 out_is_f32.  tiles: int32[3 * n_tiles] = {entry, 64-row tile, 64-column tile}. */
+#define XPS_APPLY_GROUPED_WORDS 12
+int xps_apply_grouped_f64(const int64_t* entries, int n_entries, const int32_t* tiles, int n_tiles, void* stream);
+/* n_segments means of float64 rows: out[e] = (sum over i in [begin, end) of src[trials[i] * row_len + e]) / (end - begin),
+ * added in list order in float64 (zeros for an empty list).  Words of a segment (XPS_CND_AVG_FOLDS_WORDS each): 0 src,
+ * 1 row_len, 2 out (row_len doubles), 3 begin, 4 end (into the device int32 array `trials`).  At most 65535 segments. */
+#define XPS_CND_AVG_FOLDS_WORDS 8
+int xps_cnd_avg_folds_f64(const int64_t* segments, int n_segments, const int32_t* trials, int64_t max_row_len,
+                          void* stream);
 /* One-sided Jacobi (Hestenes) on a column-major m x n float64 matrix W (n <= m is not
  * required): rotates column pairs of W and of V (n x n, column-major, identity on
  * entry) until all pairs are orthogonal.  On exit W = U * diag(sigma), V = right
