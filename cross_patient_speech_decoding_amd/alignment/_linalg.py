@@ -724,6 +724,88 @@ def cnd_avg_folds(segments):
              int(tab[s0:s0 + cnt, 1].max()), stream())
 
 
+PREFIX_WORDS, PREFIX_TILE = 8, 16                            # XPS_PREFIX_KERNELS_WORDS of include/xps.h; the kernel's tile
+
+
+def gram_center_folds(G, folds):
+    """G (N, N) float64 device Gram matrix of all rows about one centre; folds: list of (training rows, held-out rows).  ONE
+    xps_gram_center_folds_f64 call.  Returns (Kc, offsets): fold f's (n_all_f, n_tr_f) matrix -- the Gram matrix of its rows
+    (training rows first) about the mean of its training rows -- is Kc[offsets[f]:offsets[f + 1]].view(n_all_f, n_tr_f)."""
+    _check_matrix(G, 'gram_center_folds G')
+    N = G.shape[0]
+    if G.dtype != F64 or G.shape[1] != N or N < 1:
+        raise ValueError('gram_center_folds: a square float64 device matrix is needed')
+    lists, fold_off, n_train, offs = [], [0], [], [0]
+    for tr, te in folds:
+        tr, te = np.asarray(tr, dtype=np.int64).reshape(-1), np.asarray(te, dtype=np.int64).reshape(-1)
+        both = np.concatenate([tr, te])
+        if len(tr) < 1 or both.min() < 0 or both.max() >= N:
+            raise ValueError('gram_center_folds: a fold without training rows, or a row index outside the Gram matrix')
+        lists.append(both.astype(np.int32))
+        fold_off.append(fold_off[-1] + len(both))
+        n_train.append(len(tr))
+        offs.append(offs[-1] + len(both) * len(tr))
+    if fold_off[-1] >= 2 ** 31:
+        raise ValueError('gram_center_folds: the row lists must fit int32 offsets')
+    dev = G.device
+    Kc = torch.empty(offs[-1], dtype=F64, device=dev)
+    if not lists:
+        return Kc, np.asarray(offs, dtype=np.int64)
+    rows_d = torch.from_numpy(np.concatenate(lists)).to(dev)
+    fold_off_h, n_train_h = np.asarray(fold_off, dtype=np.int32), np.asarray(n_train, dtype=np.int32)      # host arrays of the call
+    nb = int(lib().xps_gram_center_folds_f64_workspace(len(lists), fold_off[-1]))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=dev)
+    call('xps_gram_center_folds_f64', G.data_ptr(), G.stride(0), N, rows_d.data_ptr(), fold_off_h.ctypes.data, n_train_h.ctypes.data,
+         len(lists), Kc.data_ptr(), ws.data_ptr(), nb, stream())
+    return Kc, np.asarray(offs, dtype=np.int64)
+
+
+def prefix_kernels(problems, rbf, K):
+    """problems: list of (Z, cuts): Z an (n, R) float64 device matrix with contiguous rows, cuts a list of (r, outputs) with r
+    ascending in 1..R and outputs a list of (gamma, dest): the n x n linear (rbf=False) or rbf kernel matrix of Z[:, :r] is
+    written at element dest of the flat float64 device buffer K.  ONE xps_prefix_kernels_f64 call.  Returns the host tables of
+    the call, which the caller keeps until it has synchronised with the stream (the library copies them on the stream)."""
+    if not (isinstance(K, torch.Tensor) and K.is_cuda and K.dtype == F64 and K.dim() == 1 and K.is_contiguous()):
+        raise ValueError('prefix_kernels: K must be a flat contiguous float64 device buffer')
+    P = len(problems)
+    if P == 0:
+        return None
+    tab = np.zeros((P, PREFIX_WORDS), dtype=np.int64)
+    cuts, cut_out, gammas, dest, tiles = [], [0], [], [], []
+    for p, (Z, cut_list) in enumerate(problems):
+        _check_matrix(Z, 'prefix_kernels Z')
+        n, R = Z.shape
+        if Z.dtype != F64 or n < 1 or R < 1 or not cut_list:
+            raise ValueError('prefix_kernels: a float64 score matrix with rows, columns and at least one cut is needed')
+        tab[p] = [Z.data_ptr(), Z.stride(0), n, R, len(cuts), len(cuts) + len(cut_list), 0, 0]
+        prev = 0
+        for r, outs in cut_list:
+            if not prev < int(r) <= R:
+                raise ValueError('prefix_kernels: cuts must ascend within 1..R')
+            prev = int(r)
+            cuts.append(prev)
+            for gamma, d in outs:
+                if not (0 <= float(gamma) < np.inf and 0 <= int(d) and int(d) + n * n <= K.numel()):
+                    raise ValueError('prefix_kernels: a gamma is negative or not finite, or an output reaches outside K')
+                gammas.append(float(gamma))
+                dest.append(int(d))
+            cut_out.append(len(dest))
+        nt = -(-n // PREFIX_TILE)
+        t = np.empty((nt, nt, 3), dtype=np.int32)
+        t[..., 0] = p
+        t[..., 1] = np.arange(nt)[:, None]
+        t[..., 2] = np.arange(nt)[None, :]
+        tiles.append(t.reshape(-1, 3))
+    host = (np.ascontiguousarray(tab.reshape(-1)), np.asarray(cuts, dtype=np.int32), np.asarray(cut_out, dtype=np.int32),
+            np.asarray(gammas + [0.0], dtype=np.float64), np.asarray(dest + [0], dtype=np.int64), np.ascontiguousarray(np.concatenate(tiles)))
+    n_out, n_tiles = len(dest), len(host[5])
+    nb = int(lib().xps_prefix_kernels_f64_workspace(P, len(cuts), n_out, n_tiles))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=K.device)
+    call('xps_prefix_kernels_f64', host[0].ctypes.data, P, host[1].ctypes.data, host[2].ctypes.data, len(cuts), host[3].ctypes.data,
+         host[4].ctypes.data, n_out, host[5].ctypes.data, n_tiles, int(bool(rbf)), K.data_ptr(), K.numel(), ws.data_ptr(), nb, stream())
+    return host + (ws,)
+
+
 def eigh_psd_stack(Cs):
     """eigh_psd of equally sized PSD matrices given as ONE (batch, n, n) float64 ndarray: one upload, one Jacobi launch, one
     download (eigh_psd_batched uploads and shifts matrix by matrix).  Sizes beyond the one-workgroup kernel go through

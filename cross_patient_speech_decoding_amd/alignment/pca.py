@@ -7,18 +7,46 @@ rule (largest-|.| entry of each component positive) and component-count rule for
 fraction (``searchsorted(cumsum(ratio), n, side='right') + 1``) -> transform = (X - mean) W on the
 device (xps_apply_f64).  This is exactly what sklearn's 'covariance_eigh' solver computes; where
 sklearn would pick its unseeded randomized solver this class returns the exact answer instead.
+
+``solver='gram'`` is the same PCA from the sample side, for wide data (the flattened trials behind ``DimRedReshape``: 144 rows of
+22 200 features, whose covariance would be a 3.9 GB matrix): centred rows -> G = Xc Xc^T (n x n, f64 MFMA GEMM) -> Jacobi ->
+explained variance L / (n - 1), components (Xc^T U_k) L_k^-1/2 by one device product.  The direction of a component with
+eigenvalue L_i carries an error of about eps * L_0 / L_i, so a kept component below L_0 / PCA_SPECTRUM_LIMIT is refused.
+``solver='auto'`` takes the Gram side when there are more features than rows; ``GramPCA`` is the class whose default that is.
 """
 import numpy as np
 
 from . import _linalg as LA
 
+SOLVERS = ('covariance', 'gram', 'auto')
+PCA_SPECTRUM_LIMIT = 1e6            # a kept Gram-side component needs L_i >= L_0 / this: direction error eps * L_0 / L_i <= ~1e-10
+
+
+def count_components(n_components, ratio, n, d):
+    """The class's component-count rule: ``ratio`` is the explained-variance-ratio curve of the fit, (n, d) the shape of X."""
+    if n_components is None:
+        k = min(n, d)
+    elif 0 < n_components < 1:
+        k = int(np.searchsorted(np.cumsum(ratio), n_components, side='right') + 1)
+    else:
+        k = int(n_components)
+    return max(1, min(k, d))
+
+
+def gram_ratio(L, n, d):
+    """The ratio curve of a Gram-side spectrum L (descending): over the min(n, d) leading eigenvalues, clipped at 0."""
+    L = np.clip(np.asarray(L, dtype=np.float64)[:min(n, d)], 0.0, None)
+    total = L.sum()
+    return L / total if total > 0 else np.zeros_like(L)
+
 
 class PCA:
-    def __init__(self, n_components=None, **_ignored):
+    def __init__(self, n_components=None, solver='covariance', **_ignored):
         self.n_components = n_components
+        self.solver = solver
 
     def get_params(self, deep=True):
-        return {'n_components': self.n_components}
+        return {'n_components': self.n_components, 'solver': self.solver}
 
     def set_params(self, **params):
         for k, v in params.items():
@@ -29,7 +57,11 @@ class PCA:
         Xd = LA.to_device(X)
         Xd = Xd.reshape(-1, Xd.shape[-1])
         n, d = Xd.shape
+        if self.solver not in SOLVERS:
+            raise ValueError(f'solver must be one of {SOLVERS}; got {self.solver!r}')
         mean = LA.col_mean(Xd)
+        if self.solver == 'gram' or (self.solver == 'auto' and d > n):
+            return self._fit_gram(Xd, mean)
         cov = LA.xcov(Xd, None, mean) / (n - 1)
         w, V = LA.eigh_psd(cov)
         w = np.clip(w, 0.0, None)
@@ -40,19 +72,42 @@ class PCA:
         comps *= signs[:, None]
         total = w.sum()
         ratio = w / total if total > 0 else np.zeros_like(w)
-        nc = self.n_components
-        if nc is None:
-            k = min(n, d)
-        elif 0 < nc < 1:
-            k = int(np.searchsorted(np.cumsum(ratio), nc, side='right') + 1)
-        else:
-            k = int(nc)
-        k = max(1, min(k, d))
+        k = count_components(self.n_components, ratio, n, d)
         self.mean_ = mean.cpu().numpy()
         self.components_ = comps[:k]
         self.explained_variance_ = w[:k]
         self.explained_variance_ratio_ = ratio[:k]
         self.singular_values_ = np.sqrt(w[:k] * (n - 1))
+        self.n_components_ = k
+        self.n_features_in_ = d
+        self.n_samples_ = n
+        self._mean_d = mean
+        self._W_d = LA.to_device(np.ascontiguousarray(self.components_.T))
+        return self
+
+    def _fit_gram(self, Xd, mean):
+        n, d = Xd.shape
+        Xc = Xd.to(LA.F64) - mean
+        G = LA.dgemm(Xc, Xc, tb=True)
+        w, U = LA.eigh_psd(0.5 * (G + G.t()))
+        w = np.clip(w, 0.0, None)
+        ratio = gram_ratio(w, n, d)
+        k = min(count_components(self.n_components, ratio, n, d), n)
+        if not w[k - 1] >= w[0] / PCA_SPECTRUM_LIMIT or w[k - 1] <= 0:
+            raise ValueError(f"component {k - 1} of the {k} kept has the eigenvalue {w[k - 1]:.3e} against {w[0]:.3e} of the first: "
+                             f"below 1 / {PCA_SPECTRUM_LIMIT:g} of it the Gram side (solver='gram') cannot resolve its direction.  "
+                             "Ask for fewer components or use solver='covariance'")
+        Wk = LA.to_device(np.ascontiguousarray(U[:, :k] / np.sqrt(w[:k])))
+        comps = LA.dgemm(Wk, Xc, ta=True).cpu().numpy()           # (Xc^T U_k) L_k^-1/2 as rows: one device product
+        idx = np.argmax(np.abs(comps), axis=1)
+        signs = np.sign(comps[np.arange(k), idx])
+        signs[signs == 0] = 1
+        comps *= signs[:, None]
+        self.mean_ = mean.cpu().numpy()
+        self.components_ = comps
+        self.explained_variance_ = w[:k] / (n - 1)
+        self.explained_variance_ratio_ = ratio[:k]
+        self.singular_values_ = np.sqrt(w[:k])
         self.n_components_ = k
         self.n_features_in_ = d
         self.n_samples_ = n
@@ -80,3 +135,11 @@ class PCA:
         Zd = LA.to_device(Z)
         W = LA.to_device(np.ascontiguousarray(self.components_))
         return (LA.apply(Zd, W) + self._mean_d).cpu().numpy()
+
+
+class GramPCA(PCA):
+    """``PCA`` whose default solver is ``'auto'``: ``DimRedReshape`` builds its reducer as ``dim_red(n_components=...)``, so the class
+    itself carries the choice -- ``DimRedReshape(GramPCA)`` runs at the width of the flattened trials."""
+
+    def __init__(self, n_components=None, solver='auto', **_ignored):
+        super().__init__(n_components=n_components, solver=solver)

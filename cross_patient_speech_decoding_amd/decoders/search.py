@@ -18,7 +18,16 @@ per chunk    (all models = (candidate, fold) pairs whose kernel matrices fit ``m
 Scores, ranks and ``cv_results_`` are assembled on the host from the confusion tables.  The per-fold rules are ``SVC.fit``'s
 applied to the fold's training rows (``gamma='scale'``, ``class_weight='balanced'``, class members in original order, libsvm's pair
 order, fewer pairs for a fold that lost a class), posed by the builder ``SVC.fit`` uses and solved by the same driver
-(decoders/_ovo.py).  There is no CPU fallback."""
+(decoders/_ovo.py).  There is no CPU fallback.
+
+``batch_pca=True`` takes the ``DimRedReshape(PCA)`` step in front of the SVC into the device problem as well.
+With more features than rows a fold's PCA lives on the sample side: the centred Gram matrix of any training set is a sub-block,
+centred again, of ONE Gram matrix of all flattened trials (``xps_gram_center_folds_f64``); one eigendecomposition per fold,
+Kc_tr,tr = U L U^T, serves every ``n_components`` (they differ in where the spectrum is cut); Z = Kc U_R L_R^-1/2 holds the PCA
+scores of the fold's training and held-out rows (``xps_apply_grouped_f64``), the view of a candidate with r components is the
+column prefix Z[:, :r], and ``xps_prefix_kernels_f64`` writes the kernel matrices of every prefix and every gamma of a chunk from
+one pass over Z.  sklearn's sign rule only flips columns, which neither kernel sees, and ``gamma='scale'`` is n_tr / sum_{i<r} L_i
+because the score columns have zero mean and squared norms L_i."""
 import numpy as np
 import torch
 from scipy.stats import rankdata
@@ -29,6 +38,8 @@ from sklearn.pipeline import Pipeline
 from .._dev import stream
 from .._lib import call, lib
 from ..alignment import _linalg as LA
+from ..alignment.pca import PCA, PCA_SPECTRUM_LIMIT, count_components, gram_ratio
+from ..decomposition.DimRedReshape import DimRedReshape
 from . import _ovo
 from .svm import SVC
 
@@ -82,6 +93,49 @@ def split_params(estimator, params):
     return batched, outer
 
 
+def pca_step_of(estimator):
+    """(name, step) of the ``DimRedReshape(PCA)`` in front of the SVC, the only pipeline ``batch_pca=True`` takes."""
+    if not (isinstance(estimator, Pipeline) and len(estimator.steps) == 2 and isinstance(estimator.steps[0][1], DimRedReshape)
+            and isinstance(estimator.steps[1][1], SVC)):
+        raise ValueError('batch_pca=True needs a Pipeline of exactly DimRedReshape(dim_red) and a decoders.SVC')
+    red = estimator.steps[0][1].dim_red
+    if not (isinstance(red, type) and issubclass(red, PCA)):
+        raise ValueError(f'batch_pca=True needs DimRedReshape over alignment.PCA or a subclass of it; got {red!r}')
+    return estimator.steps[0]
+
+
+def split_params_pca(estimator, params):
+    """``split_params`` with ``<dimredreshape>__n_components`` batched too (as ``n_components``); any other outer key raises."""
+    name, _ = pca_step_of(estimator)
+    batched, outer = split_params(estimator, params)
+    key = name + '__n_components'
+    if key in outer:
+        batched['n_components'] = outer.pop(key)
+    if outer:
+        raise ValueError(f'batch_pca=True batches {key!r}, C and gamma only; got {sorted(outer)}')
+    return batched, outer
+
+
+def pca_cut(L, n_components, n_tr, d):
+    """(r, batched) of one (fold, ``n_components``) from the fold's Gram-side spectrum L (descending, n_tr values): r by the PCA
+    class's rule (None for ``n_components=None``); batched when 1 <= r <= min(n_tr - 1, d) and L[r - 1] >= L[0] /
+    PCA_SPECTRUM_LIMIT, else the pair takes the per-(outer, fold) view path."""
+    if n_components is None:
+        return None, False
+    L = np.clip(np.asarray(L, dtype=np.float64), 0.0, None)
+    r = count_components(n_components, gram_ratio(L, n_tr, d), n_tr, d)
+    return r, bool(1 <= r <= min(n_tr - 1, d) and L[0] > 0 and L[r - 1] >= L[0] / PCA_SPECTRUM_LIMIT)
+
+
+def pca_gamma(kernel, gamma, L, r, n_tr):
+    """``_ovo.gamma_value`` on the r leading PCA scores of a fold's n_tr training rows, from the spectrum alone: the score columns
+    have zero mean and squared norms L_i, so ``'scale'`` = 1 / (r * var) = n_tr / sum_{i<r} L_i; ``'auto'`` = 1 / r."""
+    if kernel == 'rbf' and isinstance(gamma, str) and gamma in ('scale', 'auto'):
+        total = float(np.clip(np.asarray(L[:r], dtype=np.float64), 0.0, None).sum())
+        return (n_tr / total if total != 0 else 1.0) if gamma == 'scale' else 1.0 / r
+    return _ovo.gamma_value(kernel, gamma, None)
+
+
 def _same_outer(a, b):
     if a.keys() != b.keys():
         return False
@@ -99,6 +153,10 @@ class Plan:
     def __init__(self):
         self.views, self.matrices, self.models = [], [], []
         self._matrix_of = {}
+        self.pca = None                                         # build_plan_pca: a matrix's view is then ('pca', fold, r) or an index
+
+    def rows(self, view):
+        return self.pca['n_all'][view[1]] if isinstance(view, tuple) else self.views[view].shape[0]
 
     def matrix(self, view, gamma):
         key = (view, float(gamma))
@@ -108,20 +166,42 @@ class Plan:
         return self._matrix_of[key]
 
     def matrix_bytes(self):
-        return [8 * self.views[v].shape[0] ** 2 for v, _ in self.matrices]
+        return [8 * self.rows(v) ** 2 for v, _ in self.matrices]
 
 
-def build_plan(estimator, split_candidates, X, yi, classes, splits):
+def _fold_problems(svc, yi, classes, tr, train_pos):
+    """SVC.fit's rules on THIS fold's rows: its classes, its 'balanced' weights; pair_a / pair_b as indices into ``classes``."""
+    cls, yi_tr = np.unique(yi[tr], return_inverse=True)
+    problems = _ovo.pair_problems(yi_tr, train_pos, _ovo.class_weights(svc.class_weight, classes[cls], yi_tr))
+    problems['pair_a'], problems['pair_b'] = (cls[problems[key]].astype(np.int32) for key in ('pair_a', 'pair_b'))
+    return problems
+
+
+def _fit_view(estimator, outer, X, yi, classes, tr, te):
+    """What Pipeline.fit / predict do with the steps before the last, for one (outer combination, fold): the transformed
+    training rows followed by the transformed held-out rows, and the training rows alone."""
+    steps = [step for _, step in clone(estimator).set_params(**outer).steps[:-1] if step is not None and step != 'passthrough']
+    Ztr, Zte = X[tr], X[te]
+    for step in steps:
+        Ztr = step.fit_transform(Ztr, classes[yi[tr]]) if hasattr(step, 'fit_transform') else step.fit(Ztr, classes[yi[tr]]).transform(Ztr)
+        Zte = step.transform(Zte) if len(te) else Zte
+    Ztr = np.asarray(Ztr, dtype=np.float64)
+    Zte = np.asarray(Zte, dtype=np.float64) if len(te) else np.empty((0, Ztr.shape[1]))
+    if Ztr.ndim != 2 or Zte.shape[1] != Ztr.shape[1]:
+        raise ValueError('the pipeline steps before the SVC must produce (n_samples, n_features)')
+    return np.ascontiguousarray(np.vstack([Ztr, Zte])), Ztr
+
+
+def build_plan(estimator, split_candidates, X, yi, classes, splits, plan=None, only=None):
     """Views, kernel matrices and models of a search (host; a pipeline's earlier steps are fitted here, once per (outer
-    combination, fold)).  ``split_candidates``: ``split_params`` of every candidate; ``yi``: class indices of y into ``classes``."""
+    combination, fold)).  ``split_candidates``: ``split_params`` of every candidate; ``yi``: class indices of y into ``classes``.
+    ``plan`` / ``only`` (build_plan_pca): append to this plan, and only the (candidate, fold) pairs of ``only``."""
     svc, _, pre = svc_of(estimator)
-    plan = Plan()
+    plan = Plan() if plan is None else plan
     gamma_cache = {}
 
     def add_models(view, fold, cands, Ztr, train_pos, test_pos, tr, te):
-        cls, yi_tr = np.unique(yi[tr], return_inverse=True)   # SVC.fit's rules on THIS fold's rows: its classes, its 'balanced' weights
-        problems = _ovo.pair_problems(yi_tr, train_pos, _ovo.class_weights(svc.class_weight, classes[cls], yi_tr))
-        problems['pair_a'], problems['pair_b'] = (cls[problems[key]].astype(np.int32) for key in ('pair_a', 'pair_b'))
+        problems = _fold_problems(svc, yi, classes, tr, train_pos)
         for c in cands:
             batched = split_candidates[c][0]
             spec = batched.get('gamma', svc.gamma)
@@ -152,17 +232,82 @@ def build_plan(estimator, split_candidates, X, yi, classes, splits):
             outers.append((outer, [c]))
     for outer, members in outers:
         for f, (tr, te) in enumerate(splits):
-            steps = [step for _, step in clone(estimator).set_params(**outer).steps[:-1] if step is not None and step != 'passthrough']
-            Ztr, Zte = X[tr], X[te]
-            for step in steps:                                  # what Pipeline.fit / predict do with the steps before the last
-                Ztr = step.fit_transform(Ztr, classes[yi[tr]]) if hasattr(step, 'fit_transform') else step.fit(Ztr, classes[yi[tr]]).transform(Ztr)
-                Zte = step.transform(Zte) if len(te) else Zte
-            Ztr = np.asarray(Ztr, dtype=np.float64)
-            Zte = np.asarray(Zte, dtype=np.float64) if len(te) else np.empty((0, Ztr.shape[1]))
-            if Ztr.ndim != 2 or Zte.shape[1] != Ztr.shape[1]:
-                raise ValueError('the pipeline steps before the SVC must produce (n_samples, n_features)')
-            plan.views.append(np.ascontiguousarray(np.vstack([Ztr, Zte])))
-            add_models(len(plan.views) - 1, f, members, Ztr, np.arange(len(tr)), len(tr) + np.arange(len(te)), tr, te)
+            wanted = members if only is None else [c for c in members if (c, f) in only]
+            if not wanted:
+                continue
+            view, Ztr = _fit_view(estimator, outer, X, yi, classes, tr, te)
+            plan.views.append(view)
+            add_models(len(plan.views) - 1, f, wanted, Ztr, np.arange(len(tr)), len(tr) + np.arange(len(te)), tr, te)
+    return plan
+
+
+def build_plan_pca(estimator, split_candidates, X, yi, classes, splits):
+    """The plan of a ``batch_pca=True`` search.  Device: one upload of X, the column mean, one Gram product, one centring launch
+    for all folds, the Jacobi launches (one per distinct training size) and one grouped apply for the scores Z_f of every fold.
+    Host: per (fold, n_components) the cut r and whether it is batched (``pca_cut``), gamma from the spectrum (``pca_gamma``).  A
+    batched (fold, r, gamma) is a kernel matrix whose view is ``('pca', fold, r)``; the other (candidate, fold) pairs go through
+    ``build_plan``'s views inside the same plan.  ``split_candidates``: ``split_params_pca`` of every candidate."""
+    svc = svc_of(estimator)[0]
+    name, red = pca_step_of(estimator)
+    if X.ndim < 2:
+        raise ValueError('X must be (n_samples, ...)')
+    Xd = LA.to_device(X.reshape(X.shape[0], -1))
+    d = Xd.shape[1]
+    Xc = Xd.to(LA.F64) - LA.col_mean(Xd)                        # about ONE provisional centre, the all-trial mean
+    G = LA.dgemm(Xc, Xc, tb=True)
+    Kc, offs = LA.gram_center_folds(G, splits)
+    Kc_h = Kc.cpu().numpy()
+    nf = len(splits)
+    n_tr = [len(tr) for tr, _ in splits]
+    n_all = [len(tr) + len(te) for tr, te in splits]
+    blocks = [Kc_h[offs[f]:offs[f + 1]].reshape(n_all[f], n_tr[f])[:n_tr[f]] for f in range(nf)]
+    eig = [None] * nf
+    for size in sorted(set(n_tr)):                              # stacked by size: folds differ in size by one
+        fs = [f for f in range(nf) if n_tr[f] == size]
+        for f, res in zip(fs, LA.eigh_psd_stack(np.stack([0.5 * (blocks[f] + blocks[f].T) for f in fs]))):
+            eig[f] = res
+    plan = Plan()
+    ncs = [b.get('n_components', red.n_components) for b, _ in split_candidates]
+    comps = np.zeros((len(ncs), nf), dtype=np.int64)
+    cuts, fallbacks, only = [], [], set()
+    for f in range(nf):
+        cuts.append({})
+        for c, nc in enumerate(ncs):
+            if nc not in cuts[f]:
+                cuts[f][nc] = pca_cut(eig[f][0], nc, n_tr[f], d)
+                if not cuts[f][nc][1]:
+                    fallbacks.append((f, nc))
+            if not cuts[f][nc][1]:
+                only.add((c, f))
+    R = [max([r for r, ok in cuts[f].values() if ok], default=0) for f in range(nf)]
+    W_h = [eig[f][1][:, :R[f]] / np.sqrt(eig[f][0][:R[f]]) for f in range(nf)]                  # U_R L_R^-1/2
+    w_off = np.concatenate([[0], np.cumsum([w.size for w in W_h])])
+    z_off = np.concatenate([[0], np.cumsum([n_all[f] * R[f] for f in range(nf)])])
+    Wbuf = LA.to_device(np.concatenate([w.ravel() for w in W_h] + [np.zeros(1)]))
+    Zbuf = torch.empty(int(z_off[-1]) + 1, dtype=torch.float64, device=Xd.device)
+    Z = [Zbuf[z_off[f]:z_off[f + 1]].view(n_all[f], R[f]) if R[f] else None for f in range(nf)]
+    LA.apply_grouped([(Kc[offs[f]:offs[f + 1]].view(n_all[f], n_tr[f]), None, Wbuf[w_off[f]:w_off[f + 1]].view(n_tr[f], R[f]), Z[f])
+                      for f in range(nf) if R[f]])
+    plan.pca = dict(n_all=n_all, Z=Z, spectra=[e[0] for e in eig])
+    for f, (tr, te) in enumerate(splits):
+        problems = _fold_problems(svc, yi, classes, tr, np.arange(n_tr[f]))
+        for c, (batched, _) in enumerate(split_candidates):
+            r, ok = cuts[f][ncs[c]]
+            if not ok:
+                continue
+            comps[c, f] = r
+            gamma = pca_gamma(svc.kernel, batched.get('gamma', svc.gamma), eig[f][0], r, n_tr[f])
+            plan.models.append(dict(cand=c, fold=f, matrix=plan.matrix(('pca', f, r), gamma), C=float(batched.get('C', svc.C)),
+                                    problems=problems, test_pos=(n_tr[f] + np.arange(len(te))).astype(np.int32),
+                                    ytest=yi[te].astype(np.int32)))
+    if only:                                                    # the pairs that are not batched: the per-(outer, fold) views
+        key = name + '__n_components'
+        first = len(plan.models)
+        build_plan(estimator, [({k: v for k, v in b.items() if k != 'n_components'}, {key: b['n_components']} if 'n_components' in b else {})
+                               for b, _ in split_candidates], X, yi, classes, splits, plan=plan, only=only)
+        for mod in plan.models[first:]:
+            comps[mod['cand'], mod['fold']] = plan.views[plan.matrices[mod['matrix']][0]].shape[1]
+    plan.pca.update(n_components=comps, fallbacks=fallbacks)
     return plan
 
 
@@ -238,13 +383,18 @@ def _run_chunk(plan, mats, kernel, tol, svc_max_iter, k):
     """Kernel matrices ``mats`` (adjacent per view) and all their models: per view an upload, a Gram product and, for rbf, one
     multi-gamma launch; then one SMO launch, one scoring launch and one download.  Returns (models, conf (S, k, k), pred, tst_off)."""
     dev = LA.device()
-    sizes = [plan.views[plan.matrices[m][0]].shape[0] ** 2 for m in mats]
+    sizes = [plan.rows(plan.matrices[m][0]) ** 2 for m in mats]
     base = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     Kbuf = torch.empty(int(base[-1]), dtype=torch.float64, device=dev)
     slot = {m: i for i, m in enumerate(mats)}
     i = 0
+    prefixes = {}                                               # fold -> {cut r: [(gamma, first element in Kbuf)]} of the batched PCA
     while i < len(mats):                                        # one pass per view of the chunk
         v = plan.matrices[mats[i]][0]
+        if isinstance(v, tuple):
+            prefixes.setdefault(v[1], {}).setdefault(v[2], []).append((plan.matrices[mats[i]][1], int(base[i])))
+            i += 1
+            continue
         j = i
         while j < len(mats) and plan.matrices[mats[j]][0] == v:
             j += 1
@@ -259,12 +409,14 @@ def _run_chunk(plan, mats, kernel, tol, svc_max_iter, k):
         else:
             Kbuf[int(base[i]):int(base[i]) + n * n].copy_(G.view(-1))
         i = j
+    # every (fold, cut, gamma) matrix of the chunk from ONE launch; its host tables live until the download below
+    tables = LA.prefix_kernels([(plan.pca['Z'][f], sorted(cuts.items())) for f, cuts in prefixes.items()], kernel == 'rbf', Kbuf)  # noqa: F841
     models = [mod for mod in plan.models if mod['matrix'] in slot]
     models.sort(key=lambda mod: slot[mod['matrix']])            # (stable: plan order inside a matrix)
     S = len(models)
     probs = [mod['problems'] for mod in models]
     nprob = np.array([len(p['npos']) for p in probs], dtype=np.int64)
-    mn = np.array([plan.views[plan.matrices[mod['matrix']][0]].shape[0] for mod in models], dtype=np.int64)
+    mn = np.array([plan.rows(plan.matrices[mod['matrix']][0]) for mod in models], dtype=np.int64)
     mbase = np.array([base[slot[mod['matrix']]] for mod in models], dtype=np.int64)
     sizes_q = _cat(probs, 'sizes')
     off = np.concatenate([[0], np.cumsum(sizes_q)])
@@ -306,10 +458,16 @@ class SVCSearchCV(BaseEstimator):
     After ``fit``: ``cv_results_``, ``best_index_``, ``best_params_``, ``best_score_``, ``n_splits_``, ``classes_``,
     ``cv_test_predictions_`` (per split: ``(test_idx, labels (n_candidates, len(test_idx)))``), ``cv_confusion_`` (n_candidates,
     n_splits, k, k; rows = true class) and, with ``refit``, ``best_estimator_`` = ``clone(estimator).set_params(**best_params_)
-    .fit(X, y)``, to which ``predict`` / ``decision_function`` / ``score`` delegate."""
+    .fit(X, y)``, to which ``predict`` / ``decision_function`` / ``score`` delegate.
+
+    ``batch_pca=True`` (the estimator must be a Pipeline of exactly ``DimRedReshape(alignment.PCA or a subclass)`` and a
+    ``decoders.SVC``): ``<dimredreshape>__n_components`` is batched beside ``C`` and ``gamma`` -- one Gram matrix of the flattened
+    trials serves all folds, one eigendecomposition per fold all component counts -- and any other outer key raises
+    ``ValueError``.  Adds ``pca_n_components_`` (n_candidates x n_splits) and ``pca_fallbacks_``, the (fold, n_components) pairs
+    that took the per-fold fit instead (``None``, a cut at or beyond the training rows' rank, or below the spectrum limit)."""
 
     def __init__(self, estimator, param_grid=None, *, candidates=None, cv=5, scoring=None, refit=True, max_kernel_bytes=2 ** 30,
-                 return_train_score=False, error_score=np.nan):
+                 return_train_score=False, error_score=np.nan, batch_pca=False):
         self.estimator = estimator
         self.param_grid = param_grid
         self.candidates = candidates
@@ -319,6 +477,7 @@ class SVCSearchCV(BaseEstimator):
         self.max_kernel_bytes = max_kernel_bytes
         self.return_train_score = return_train_score
         self.error_score = error_score
+        self.batch_pca = batch_pca
 
     def _check_settings(self):
         svc, _, _ = svc_of(self.estimator)
@@ -336,7 +495,7 @@ class SVCSearchCV(BaseEstimator):
             raise NotImplementedError(f'fit parameters ({sorted(fit_params)}) are not implemented on the HIP path')
         svc = self._check_settings()
         candidates = expand_candidates(self.param_grid, self.candidates)
-        split_candidates = [split_params(self.estimator, c) for c in candidates]
+        split_candidates = [(split_params_pca if self.batch_pca else split_params)(self.estimator, c) for c in candidates]
         X, y = np.asarray(X), np.asarray(y)
         if y.ndim != 1 or X.shape[0] != y.shape[0]:
             raise ValueError('X must have one row per element of y (n_samples,)')
@@ -350,7 +509,7 @@ class SVCSearchCV(BaseEstimator):
         splits = [(np.asarray(tr), np.asarray(te)) for tr, te in cv.split(X, y)]
         if not splits:
             raise ValueError('cv yields no split')
-        plan = build_plan(self.estimator, split_candidates, X, yi, classes, splits)
+        plan = (build_plan_pca if self.batch_pca else build_plan)(self.estimator, split_candidates, X, yi, classes, splits)
         # ---- the device: no loop over candidates or folds below, only over views (uploads) and chunks
         conf = np.zeros((len(candidates), len(splits), k, k), dtype=np.int32)
         labels = [np.empty((len(candidates), len(te)), dtype=classes.dtype) for _, te in splits]
@@ -362,6 +521,8 @@ class SVCSearchCV(BaseEstimator):
         scores = scores_from_confusion(conf, self.scoring)
         self.cv_results_ = assemble_results(candidates, scores)
         self.cv_confusion_ = conf
+        if self.batch_pca:
+            self.pca_n_components_, self.pca_fallbacks_ = plan.pca['n_components'], plan.pca['fallbacks']
         self.cv_test_predictions_ = [(te, lab) for (_, te), lab in zip(splits, labels)]
         self.n_splits_ = len(splits)
         self.classes_ = classes

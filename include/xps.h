@@ -559,6 +559,44 @@ int xps_apply_grouped_f64(const int64_t* entries, int n_entries, const int32_t* 
 #define XPS_CND_AVG_FOLDS_WORDS 8
 int xps_cnd_avg_folds_f64(const int64_t* segments, int n_segments, const int32_t* trials, int64_t max_row_len,
                           void* stream);
+/* Fold-batched PCA in front of the SVC search (decoders/search.py, batch_pca=True: the DimRedReshape(PCA) step of
+ * scripts/aligned_decode_svm_ncv.py:171-177 for all folds and all n_components at once).
+ *
+ * xps_gram_center_folds_f64: G is the N x N Gram matrix (leading dimension ldg >= N) of all rows about ONE centre.  Fold f owns the
+ * entries rows[fold_off[f] .. fold_off[f + 1]) of the DEVICE int32 list `rows`: its n_train[f] training rows, then its held-out
+ * rows (n_all_f in all; a fold may have no held-out rows; the order inside a fold is the caller's).  It receives the dense
+ * n_all_f x n_train[f] matrix
+ *   Kc_f[a][b] = ((G[r_a][r_b] - m[a]) - m[b]) + mm,   m[a] = (1 / n_tr) sum_{t < n_tr} G[r_a][r_t],   mm = (1 / n_tr) sum_{b < n_tr} m[b]
+ * at Kc + sum_{g < f} n_all_g * n_train[g]: the Gram matrix of the fold's rows about the mean of its training rows.  A sum is
+ * taken by one wave: lane l adds its terms l, l + 64, ... in ascending order, then the 64 partial sums meet in a fixed butterfly;
+ * no atomics, so two runs give the same bits.  fold_off (n_folds + 1) and n_train (n_folds) are HOST arrays: the call checks
+ * that fold_off ascends from 0 and 1 <= n_train[f] <= n_all_f, and copies them into ws (DEVICE,
+ * xps_gram_center_folds_f64_workspace(n_folds, fold_off[n_folds]) bytes).  The row list is checked on the device and the call
+ * WAITS for the stream to learn the verdict: a null pointer, an index outside [0, N) or a bad offset is refused with
+ * XPS_E_INVALID before anything is read through the list, so nothing outside G is read.  At most 65535 folds.
+ *
+ * xps_prefix_kernels_f64: the kernel matrices of column prefixes of score matrices.  Problem p (XPS_PREFIX_KERNELS_WORDS int64
+ * words: 0 Z (device pointer, n x R float64), 1 ldz (>= R), 2 n (>= 1), 3 R (>= 1), 4 cut_begin, 5 cut_end) owns the cuts
+ * cuts[cut_begin .. cut_end): 1 <= r_1 < r_2 < ... <= R, the lists of the problems following each other, none empty.  Cut c
+ * owns the outputs cut_out[c] .. cut_out[c + 1]) (cut_out[0] = 0, cut_out[n_cuts] = n_out); output o is the dense n x n matrix at
+ * element dest[o] of K (k_len elements; dest[o] + n * n <= k_len; the caller keeps the outputs apart):
+ *   rbf = 0:  K_o[i][j] = acc_r(i, j),   acc_r(i, j) = fma(z_i,r-1, z_j,r-1, ... fma(z_i0, z_j0, 0))      (k ascending)
+ *   rbf = 1:  K_o[i][j] = exp(-gammas[o] (acc_r(i, i) + acc_r(j, j) - 2 acc_r(i, j)))    (xps_rbf_from_gram_f64's expression)
+ * One thread owns (i, j) and carries its accumulator across the cuts, so Z is read once for all cuts and gammas, and the
+ * matrices of cut r are those of a call that has the single cut r, bit for bit; the rbf diagonal is exactly 1 and gamma = 0 gives
+ * ones.  tiles: int32[3 * n_tiles] = {problem, 16-row tile, 16-column tile} for every tile of every problem.  ALL tables
+ * (problems, cuts, cut_out, gammas, dest, tiles) are HOST arrays: the call checks them (cuts that do not ascend, a cut of 0 or
+ * beyond R, n < 1, R < 1, ldz < R, an output outside K, a negative or non-finite gamma, a tile outside its problem, null
+ * pointers: XPS_E_INVALID before any launch) and copies them into ws (DEVICE, xps_prefix_kernels_f64_workspace(...) bytes) on
+ * the stream; they must stay valid until the stream has passed the call.  Nothing synchronises. */
+size_t xps_gram_center_folds_f64_workspace(int n_folds, int64_t total_rows);
+int xps_gram_center_folds_f64(const double* G, int64_t ldg, int N, const int32_t* rows, const int32_t* fold_off,
+                              const int32_t* n_train, int n_folds, double* Kc, void* ws, size_t ws_bytes, void* stream);
+#define XPS_PREFIX_KERNELS_WORDS 8
+size_t xps_prefix_kernels_f64_workspace(int n_problems, int n_cuts, int n_out, int n_tiles);
+int xps_prefix_kernels_f64(const int64_t* problems, int n_problems, const int32_t* cuts, const int32_t* cut_out, int n_cuts,
+                           const double* gammas, const int64_t* dest, int n_out, const int32_t* tiles, int n_tiles, int rbf,
+                           double* K, int64_t k_len, void* ws, size_t ws_bytes, void* stream);
 /* One-sided Jacobi (Hestenes) on a column-major m x n float64 matrix W (n <= m is not
  * required): rotates column pairs of W and of V (n x n, column-major, identity on
  * entry) until all pairs are orthogonal.  On exit W = U * diag(sigma), V = right
