@@ -119,17 +119,22 @@ def _cca_device(La, Lb):
     Wb, s_b, V_b = LA.svd_tall_device(Lb, LA.col_mean(Lb))
     r_a = LA.rank_from_singular_values(s_a, (n, La.shape[1]))
     r_b = LA.rank_from_singular_values(s_b, (n, Lb.shape[1]))
-    d = min(r_a, r_b)
     # K = Q_a^T Q_b with Q = W^T diag(1 / s) restricted to the numerical range
     G = LA.dgemm(Wa[:r_a].contiguous(), Wb[:r_b].contiguous(), tb=True).cpu().numpy()
     K = G / s_a[:r_a, None] / s_b[None, :r_b]
     U, S, Vt = LA.svd(LA.to_device(np.ascontiguousarray(K)))
-    M_a = (V_a[:, :r_a] / s_a[:r_a]) @ U[:, :d]
-    M_b = (V_b[:, :r_b] / s_b[:r_b]) @ Vt.T[:, :d]
+    return cca_tail(V_a[:, :r_a] / s_a[:r_a], V_b[:, :r_b] / s_b[:r_b], U, S, Vt)
+
+
+def cca_tail(W_a, W_b, U, S, Vt):
+    """The end of a CCA on whitened data: W_a (d_a, r_a) and W_b (d_b, r_b) the whitening factors, (U, S, Vt) the SVD of
+    K = W_a^T C_ab W_b (r_a x r_b).  Returns M_a = W_a U[:, :d], M_b = W_b V[:, :d] and the d = min(K.shape) canonical
+    correlations clipped to [0, 1]."""
+    d = min(U.shape[0], Vt.shape[1])
     S = S[:d].copy()
     S[S < 0] = 0
     S[S >= 1] = 1
-    return M_a, M_b, S
+    return W_a @ U[:, :d], W_b @ Vt.T[:, :d], S
 
 
 def reshape_latent_dynamics(X_a, X_b, y_a, y_b, type='class'):

@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _linalg as LA
 from .alignment_utils import _group_conditions_device
+from .pca import sign_rule
 
 
 class DeviceMCCA:
@@ -79,9 +80,7 @@ class DeviceMCCA:
         Vfull = LA.to_device(np.vstack(load_red))
         common = LA.apply(Z, Vfull, mean).cpu().numpy()
         common = common / np.linalg.norm(common, axis=0)
-        rows = np.argmax(np.abs(common), axis=0)
-        signs = np.sign(common[rows, np.arange(common.shape[1])])
-        signs[signs == 0] = 1
+        signs = sign_rule(common, 0)
         self.loadings_ = [l * signs for l in load_red]
         self._load_d = [LA.to_device(np.ascontiguousarray(l)) for l in self.loadings_]
         self.n_views_ = len(Vd)

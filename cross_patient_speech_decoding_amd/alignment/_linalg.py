@@ -226,6 +226,18 @@ def chol_whiten_blocks(Gd, offs, scale, shift, LHS=None):
     return S
 
 
+def _svd_tail(W, V):
+    """(U, s, Vt) from the rotated matrix of a one-sided Jacobi SVD, W (n, m) with row j = u_j * s_j, and the rotations V (n, n)
+    with row j = v_j: the norms, a stable descending order, and U with zero columns where a singular value is zero."""
+    s = np.linalg.norm(W, axis=1)
+    order = np.argsort(-s, kind='stable')
+    s, W, V = s[order], W[order], V[order]
+    U = np.zeros_like(W)
+    nz = s > 0
+    U[nz] = W[nz] / s[nz, None]
+    return U.T, s, V
+
+
 def svd(A):
     """Thin SVD of a small float64 device matrix by one-sided Jacobi: A = U diag(s) Vt, s descending.
     Returns numpy (U, s, Vt)."""
@@ -236,15 +248,7 @@ def svd(A):
         return Vt.T, s, U.T
     Wc = A.t().contiguous().clone()                 # row j = column j of A
     Vc = _jacobi(Wc, n, m)
-    W = Wc.cpu().numpy()                            # (n, m): row j = u_j * s_j
-    V = Vc.cpu().numpy()                            # (n, n): row j = v_j
-    s = np.linalg.norm(W, axis=1)
-    order = np.argsort(-s, kind='stable')
-    s, W, V = s[order], W[order], V[order]
-    U = np.zeros_like(W)
-    nz = s > 0
-    U[nz] = W[nz] / s[nz, None]
-    return U.T, s, V
+    return _svd_tail(Wc.cpu().numpy(), Vc.cpu().numpy())
 
 
 # Eigenvectors without accumulated rotations.  After the one-sided Jacobi W = C V = V diag(w), so for a
@@ -294,20 +298,34 @@ def eigh_psd(C, well_conditioned=False):
     return w[order], V[order].T
 
 
+def _shifted_stack(Cs, well_conditioned):
+    """(Wb, sig): the (batch, n, n) device stack C + sigma I of a batch and its shifts.  An ndarray stack is shifted on the host
+    and uploaded once; a list (device tensors allowed) is stacked and shifted on the device."""
+    if isinstance(Cs, np.ndarray):
+        g = np.abs(Cs).sum(axis=-1).max(axis=-1)
+        sig = np.zeros(len(Cs)) if well_conditioned else np.where(g > 0, g * _SHIFT, 1.0)
+        return to_device(Cs + sig[:, None, None] * np.eye(Cs.shape[-1])), sig
+    Wb = torch.stack([to_device(c).to(F64) for c in Cs]).contiguous()
+    sig = [0.0 if well_conditioned else _shift_of(W) for W in Wb]
+    for W, sg in zip(Wb, sig):
+        if sg:
+            W.diagonal().add_(sg)
+    return Wb, sig
+
+
 def eigh_psd_batched(Cs, well_conditioned=False):
-    """eigh_psd of a list of equally sized small PSD matrices in one launch."""
+    """eigh_psd of equally sized small PSD matrices by ONE Jacobi launch and one download: a list of (w descending, V).  Cs is a
+    (batch, n, n) float64 ndarray or a list of matrices (ndarrays or device tensors).  Matrices of different sizes, or of a size
+    beyond the one-workgroup kernel, are decomposed one at a time."""
+    if isinstance(Cs, np.ndarray):
+        Cs = np.ascontiguousarray(Cs, dtype=np.float64)
     n = Cs[0].shape[0]
     if len({tuple(c.shape) for c in Cs}) != 1 or not lib().xps_jacobi_small_supported(n, n, 0):
         return [eigh_psd(to_device(c), well_conditioned) for c in Cs]
-    Cb = torch.stack([to_device(c).to(F64) for c in Cs]).contiguous()
-    sig = [0.0 if well_conditioned else _shift_of(Cb[i]) for i in range(len(Cs))]
-    Wb = Cb.clone()
-    for i, sg in enumerate(sig):
-        if sg:
-            Wb[i].diagonal().add_(sg)
+    Wb, sig = _shifted_stack(Cs, well_conditioned)
     jacobi_batched(Wb, want_v=False)
     res = [_eig_from_w(W, sg) for W, sg in zip(Wb.cpu().numpy(), sig)]
-    return [r if r is not None else eigh_psd(Cb[i], well_conditioned) for i, r in enumerate(res)]
+    return [r if r is not None else eigh_psd(to_device(Cs[i]), well_conditioned) for i, r in enumerate(res)]
 
 
 def _eigh_sym_top_full(C, k):
@@ -582,6 +600,19 @@ def xcov_grouped_splits(rows):
     return int(max(1, min(XCOV_MAX_SPLITS, -(-int(rows) // XCOV_SPLIT_ROWS))))
 
 
+def _tile_table(counts):
+    """The int32 table of a grouped launch, one row {problem, mt, nt[, split]} per workgroup.  counts[i]: problem i's numbers of
+    row tiles, column tiles [and splits].  Problems in order; within a problem the last index runs fastest."""
+    counts = np.asarray(counts, dtype=np.int64)
+    per = counts.prod(axis=1)
+    rest = np.arange(per.sum()) - np.repeat(np.cumsum(per) - per, per)       # position of a workgroup inside its problem
+    cols = []
+    for c in np.repeat(counts, per, axis=0).T[::-1]:
+        cols.append(rest % c)
+        rest = rest // c
+    return np.ascontiguousarray(np.stack([np.repeat(np.arange(len(per)), per)] + cols[::-1], axis=1), dtype=np.int32)
+
+
 def _check_matrix(t, what):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 and t.dtype in (torch.float32, F64)
             and (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1]):
@@ -630,13 +661,7 @@ def xcov_grouped(problems):
         blks += [ba, bb]
         nblk_tot += 2 * len(ba)
         slab_tot += splits * ln
-        mt, nt = -(-da // 64), -(-db // 64)
-        t = np.empty((mt, nt, splits, 4), dtype=np.int32)
-        t[..., 0] = i
-        t[..., 1] = np.arange(mt)[:, None, None]
-        t[..., 2] = np.arange(nt)[None, :, None]
-        t[..., 3] = np.arange(splits)[None, None, :]
-        tiles.append(t.reshape(-1, 4))
+        tiles.append((-(-da // 64), -(-db // 64), splits))
     out = torch.empty(int(offs[-1]), dtype=F64, device=dev)
     if n == 0:
         return out, offs
@@ -649,7 +674,7 @@ def xcov_grouped(problems):
     tab[:, 15] = slabs.data_ptr() + 8 * tab[:, 15]
     host = np.concatenate([tab.reshape(-1)] + blks + ([np.zeros(1, dtype=np.int64)] if nblk_tot == 0 else []))
     words.copy_(torch.from_numpy(host))
-    tiles = np.ascontiguousarray(np.concatenate(tiles))
+    tiles = _tile_table(tiles)
     tiles_d = torch.from_numpy(tiles).to(dev)
     call('xps_xcov_grouped_f64', words.data_ptr(), n, tiles_d.data_ptr(), len(tiles),
          int((offs[1:] - offs[:-1]).max()), stream())
@@ -683,14 +708,9 @@ def apply_grouped(entries):
             raise ValueError('apply_grouped: shapes of X, W and out do not fit together (W must be float64)')
         tab[i] = [X.data_ptr(), _is32(X), X.stride(0), rows, _check_vector(mean, d_in, 'apply_grouped mean'), W.data_ptr(),
                   W.stride(0), d_in, d_out, out.data_ptr(), out.stride(0), _is32(out)]
-        mt, nt = -(-rows // 64), -(-d_out // 64)
-        t = np.empty((mt, nt, 3), dtype=np.int32)
-        t[..., 0] = i
-        t[..., 1] = np.arange(mt)[:, None]
-        t[..., 2] = np.arange(nt)[None, :]
-        tiles.append(t.reshape(-1, 3))
+        tiles.append((-(-rows // 64), -(-d_out // 64)))
     dev = device()
-    tiles = np.ascontiguousarray(np.concatenate(tiles))
+    tiles = _tile_table(tiles)
     tab_d = torch.from_numpy(tab.reshape(-1)).to(dev)
     tiles_d = torch.from_numpy(tiles).to(dev)
     call('xps_apply_grouped_f64', tab_d.data_ptr(), n, tiles_d.data_ptr(), len(tiles), stream())
@@ -790,36 +810,15 @@ def prefix_kernels(problems, rbf, K):
                 gammas.append(float(gamma))
                 dest.append(int(d))
             cut_out.append(len(dest))
-        nt = -(-n // PREFIX_TILE)
-        t = np.empty((nt, nt, 3), dtype=np.int32)
-        t[..., 0] = p
-        t[..., 1] = np.arange(nt)[:, None]
-        t[..., 2] = np.arange(nt)[None, :]
-        tiles.append(t.reshape(-1, 3))
+        tiles.append((-(-n // PREFIX_TILE), -(-n // PREFIX_TILE)))
     host = (np.ascontiguousarray(tab.reshape(-1)), np.asarray(cuts, dtype=np.int32), np.asarray(cut_out, dtype=np.int32),
-            np.asarray(gammas + [0.0], dtype=np.float64), np.asarray(dest + [0], dtype=np.int64), np.ascontiguousarray(np.concatenate(tiles)))
+            np.asarray(gammas + [0.0], dtype=np.float64), np.asarray(dest + [0], dtype=np.int64), _tile_table(tiles))
     n_out, n_tiles = len(dest), len(host[5])
     nb = int(lib().xps_prefix_kernels_f64_workspace(P, len(cuts), n_out, n_tiles))
     ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=K.device)
     call('xps_prefix_kernels_f64', host[0].ctypes.data, P, host[1].ctypes.data, host[2].ctypes.data, len(cuts), host[3].ctypes.data,
          host[4].ctypes.data, n_out, host[5].ctypes.data, n_tiles, int(bool(rbf)), K.data_ptr(), K.numel(), ws.data_ptr(), nb, stream())
     return host + (ws,)
-
-
-def eigh_psd_stack(Cs):
-    """eigh_psd of equally sized PSD matrices given as ONE (batch, n, n) float64 ndarray: one upload, one Jacobi launch, one
-    download (eigh_psd_batched uploads and shifts matrix by matrix).  Sizes beyond the one-workgroup kernel go through
-    eigh_psd_batched, which decomposes them one at a time.  Returns a list of (w descending, V)."""
-    Cs = np.ascontiguousarray(Cs, dtype=np.float64)
-    b, n, _ = Cs.shape
-    if not lib().xps_jacobi_small_supported(n, n, 0):
-        return eigh_psd_batched(list(Cs))
-    g = np.abs(Cs).sum(axis=-1).max(axis=-1)
-    sig = np.where(g > 0, g * _SHIFT, 1.0)
-    Wb = to_device(Cs + sig[:, None, None] * np.eye(n))
-    jacobi_batched(Wb, want_v=False)
-    res = [_eig_from_w(W, sg) for W, sg in zip(Wb.cpu().numpy(), sig)]
-    return [r if r is not None else eigh_psd(to_device(Cs[i])) for i, r in enumerate(res)]
 
 
 def svd_batched(Ks):
@@ -833,13 +832,4 @@ def svd_batched(Ks):
         return [svd(to_device(K)) for K in Ks]
     Wb = to_device(np.ascontiguousarray(Ks.transpose(0, 2, 1)))         # [b] row j = column j of K[b]
     Vb = jacobi_batched(Wb, want_v=True)
-    out = []
-    for W, V in zip(Wb.cpu().numpy(), Vb.cpu().numpy()):
-        s = np.linalg.norm(W, axis=1)
-        order = np.argsort(-s, kind='stable')
-        s, W, V = s[order], W[order], V[order]
-        U = np.zeros_like(W)
-        nz = s > 0
-        U[nz] = W[nz] / s[nz, None]
-        out.append((U.T, s, V))
-    return out
+    return [_svd_tail(W, V) for W, V in zip(Wb.cpu().numpy(), Vb.cpu().numpy())]

@@ -30,9 +30,9 @@ import numpy as np
 import torch
 
 from . import _linalg as LA
-from .AlignCCA import _cca_device
+from .AlignCCA import _cca_device, cca_tail
 from .alignment_utils import _cnd_avg_device, label2str
-from .pca import PCA
+from .pca import PCA, count_components, sign_rule
 
 SPECTRUM_LIMIT = 1e10          # above it rank_from_gram_eigs and LAPACK's rank rule may disagree: the problem takes _cca_device
 
@@ -109,26 +109,6 @@ def fold_plan(y_align, pool_align_labels, splits):
     return plan
 
 
-def _pca_from_eigs(w, V, n_components, n, d):
-    """alignment.PCA's rules on an eigendecomposition: sklearn's sign rule and its component-count rule."""
-    w = np.clip(w, 0.0, None)
-    comps = V.T.copy()
-    idx = np.argmax(np.abs(comps), axis=1)
-    signs = np.sign(comps[np.arange(comps.shape[0]), idx])
-    signs[signs == 0] = 1
-    comps *= signs[:, None]
-    total = w.sum()
-    ratio = w / total if total > 0 else np.zeros_like(w)
-    if n_components is None:
-        k = min(n, d)
-    elif 0 < n_components < 1:
-        k = int(np.searchsorted(np.cumsum(ratio), n_components, side='right') + 1)
-    else:
-        k = int(n_components)
-    k = max(1, min(k, d))
-    return comps[:k], w[:k], ratio
-
-
 class _FoldProjector:
     """What ``process_aligner`` returns as its fitted target PCA, for one fold: mean_, components_, n_components_ and
     ``transform`` (device apply, like alignment.PCA)."""
@@ -190,7 +170,7 @@ def _solve_cca(probs):
     mats = [p['Caa'] for p in probs] + [p['Cbb'] for p in probs]
     eig = [None] * len(mats)
     for shape, idx in _by_shape(mats).items():
-        for i, r in zip(idx, LA.eigh_psd_stack(np.stack([mats[i] for i in idx]))):
+        for i, r in zip(idx, LA.eigh_psd_batched(np.stack([mats[i] for i in idx]))):
             eig[i] = r
     ready = []
     for j, p in enumerate(probs):
@@ -205,12 +185,7 @@ def _solve_cca(probs):
     for shape, idx in _by_shape([p['K'] for p in ready]).items():
         for i, (U, S, Vt) in zip(idx, LA.svd_batched(np.stack([ready[i]['K'] for i in idx]))):
             p = ready[i]
-            d = min(shape)
-            p['M_a'], p['M_b'] = p['Wa'] @ U[:, :d], p['Wb'] @ Vt.T[:, :d]
-            S = S[:d].copy()
-            S[S < 0] = 0
-            S[S >= 1] = 1
-            p['S'] = S
+            p['M_a'], p['M_b'], p['S'] = cca_tail(p['Wa'], p['Wb'], U, S, Vt)
             p['map'] = p['M_b'] @ np.linalg.pinv(p['M_a'])
 
 
@@ -262,12 +237,17 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
     fa.plan, fa._X = plan, Xd
     fa.pca_mean_, fa.pca_components_, fa.n_components_, fa.explained_variance_ = [], [], [], []
     fa.explained_variance_ratio_all_ = []
-    for f, (w, V) in enumerate(LA.eigh_psd_stack(covs)):
-        comps, ev, ratio = _pca_from_eigs(w, V, n_components, int(n_f[f]), C)
+    for f, (w, V) in enumerate(LA.eigh_psd_batched(covs)):
+        # alignment.PCA's rules on the covariance side: ratio curve w / sum(w), its component count, sklearn's sign rule
+        w = np.clip(w, 0.0, None)
+        total = w.sum()
+        ratio = w / total if total > 0 else np.zeros_like(w)
+        k = count_components(n_components, ratio, int(n_f[f]), C)
+        comps = V.T[:k].copy()
         fa.pca_mean_.append(means[f].copy())
-        fa.pca_components_.append(comps)
-        fa.n_components_.append(comps.shape[0])
-        fa.explained_variance_.append(ev)
+        fa.pca_components_.append(comps * sign_rule(comps, 1)[:, None])
+        fa.n_components_.append(k)
+        fa.explained_variance_.append(w[:k])
         fa.explained_variance_ratio_all_.append(ratio)
     kf = fa.n_components_
     flat = LA.to_device(np.concatenate([np.concatenate([fa.pca_mean_[f], fa.pca_components_[f].T.reshape(-1)])

@@ -33,6 +33,17 @@ def count_components(n_components, ratio, n, d):
     return max(1, min(k, d))
 
 
+def sign_rule(M, axis):
+    """sklearn's sign rule: the factors (+1 / -1) that make the entry of largest magnitude along ``axis`` of every vector of M
+    positive -- the first such entry on a tie; a zero entry counts as +1.  M is 2-D: axis 0 for vectors in columns, 1 for rows."""
+    M = np.asarray(M)
+    idx = np.argmax(np.abs(M), axis=axis)
+    other = np.arange(len(idx))
+    signs = np.sign(M[idx, other] if axis == 0 else M[other, idx])
+    signs[signs == 0] = 1
+    return signs
+
+
 def gram_ratio(L, n, d):
     """The ratio curve of a Gram-side spectrum L (descending): over the min(n, d) leading eigenvalues, clipped at 0."""
     L = np.clip(np.asarray(L, dtype=np.float64)[:min(n, d)], 0.0, None)
@@ -66,24 +77,10 @@ class PCA:
         w, V = LA.eigh_psd(cov)
         w = np.clip(w, 0.0, None)
         comps = V.T.copy()
-        idx = np.argmax(np.abs(comps), axis=1)
-        signs = np.sign(comps[np.arange(comps.shape[0]), idx])
-        signs[signs == 0] = 1
-        comps *= signs[:, None]
         total = w.sum()
         ratio = w / total if total > 0 else np.zeros_like(w)
         k = count_components(self.n_components, ratio, n, d)
-        self.mean_ = mean.cpu().numpy()
-        self.components_ = comps[:k]
-        self.explained_variance_ = w[:k]
-        self.explained_variance_ratio_ = ratio[:k]
-        self.singular_values_ = np.sqrt(w[:k] * (n - 1))
-        self.n_components_ = k
-        self.n_features_in_ = d
-        self.n_samples_ = n
-        self._mean_d = mean
-        self._W_d = LA.to_device(np.ascontiguousarray(self.components_.T))
-        return self
+        return self._set_fitted(mean, comps[:k], w[:k], ratio[:k], np.sqrt(w[:k] * (n - 1)), n)
 
     def _fit_gram(self, Xd, mean):
         n, d = Xd.shape
@@ -99,17 +96,16 @@ class PCA:
                              "Ask for fewer components or use solver='covariance'")
         Wk = LA.to_device(np.ascontiguousarray(U[:, :k] / np.sqrt(w[:k])))
         comps = LA.dgemm(Wk, Xc, ta=True).cpu().numpy()           # (Xc^T U_k) L_k^-1/2 as rows: one device product
-        idx = np.argmax(np.abs(comps), axis=1)
-        signs = np.sign(comps[np.arange(k), idx])
-        signs[signs == 0] = 1
-        comps *= signs[:, None]
+        return self._set_fitted(mean, comps, w[:k] / (n - 1), ratio[:k], np.sqrt(w[:k]), n)
+
+    def _set_fitted(self, mean, comps, variance, ratio, singular_values, n):
+        """The fitted attributes of either solver; comps (k, d) rows = components, their signs still the solver's."""
         self.mean_ = mean.cpu().numpy()
-        self.components_ = comps
-        self.explained_variance_ = w[:k] / (n - 1)
-        self.explained_variance_ratio_ = ratio[:k]
-        self.singular_values_ = np.sqrt(w[:k])
-        self.n_components_ = k
-        self.n_features_in_ = d
+        self.components_ = comps * sign_rule(comps, 1)[:, None]
+        self.explained_variance_ = variance
+        self.explained_variance_ratio_ = ratio
+        self.singular_values_ = singular_values
+        self.n_components_, self.n_features_in_ = comps.shape
         self.n_samples_ = n
         self._mean_d = mean
         self._W_d = LA.to_device(np.ascontiguousarray(self.components_.T))

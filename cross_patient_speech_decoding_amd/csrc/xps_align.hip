@@ -11,10 +11,8 @@
 //                         dense matrices and eigendecomposition of PSD matrices (the
 //                         whitened generalised eigenproblem of MCCA, covariance of PCA).
 //  k4  xps_apply_f64      batched transform apply  (X - mean) W  (same MFMA kernel).
-//
-// f64 MFMA operand mapping (16x16x4, lane l: n = l & 15, kq = l >> 4):
-//   A[row n][k kq], B[k kq][col n], D[row = kq + 4*i][col = n] in register i.
 #include "xps_common.h"
+#include "xps_f64_tile.h"
 
 namespace {
 
@@ -81,56 +79,13 @@ __global__ __launch_bounds__(1024) void colsum64_stage2(const double* __restrict
 }
 
 // ------------------------------------------------------------- f64 MFMA GEMM ----
-constexpr int DM = 64, DN = 64, DK = 16, DLD = 66;
-
-struct Mat64 {
-    const void* p;
-    long long ld;
-    const double* mean;   // indexed by the CONTIGUOUS (storage column) index, or null
-    int is_f32;
-};
-
-__device__ inline double ld_elem(const Mat64& m, long long off) {
-    return m.is_f32 ? (double)reinterpret_cast<const float*>(m.p)[off] : reinterpret_cast<const double*>(m.p)[off];
-}
-
-// Stage a (DK x 64) k-major tile  S[k][x]  of a matrix stored either [x][k] (KC) or [k][x].
-template <bool KC>
-__device__ inline void stage_tile(const Mat64& m, double (*S)[DLD], int x0, int X, int k0, int kend, int tid) {
-    if (KC) {
-        const int x = x0 + (tid >> 2), kb = k0 + (tid & 3) * 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = kb + i;
-            double v = 0.0;
-            if (x < X && k < kend) {
-                v = ld_elem(m, (long long)x * m.ld + k);
-                if (m.mean) v -= m.mean[k];
-            }
-            S[(tid & 3) * 4 + i][tid >> 2] = v;
-        }
-    } else {
-        const int k = k0 + (tid >> 4), xb = x0 + (tid & 15) * 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int x = xb + i;
-            double v = 0.0;
-            if (x < X && k < kend) {
-                v = ld_elem(m, (long long)k * m.ld + x);
-                if (m.mean) v -= m.mean[x];
-            }
-            S[tid >> 4][(tid & 15) * 4 + i] = v;
-        }
-    }
-}
-
+// The tile is xps_f64_tile.h's; AK / BK: the operand is stored with the contraction index contiguous.
 template <bool AK, bool BK>
 __global__ __launch_bounds__(256) void gemm_f64_kernel(Mat64 A, Mat64 B, void* __restrict__ Cp, long long ldc, int c_is_f32,
                                                        int M, int N, int K, int kchunk, long long slab_stride) {
     __shared__ __attribute__((aligned(16))) double As[DK][DLD];
     __shared__ __attribute__((aligned(16))) double Bs[DK][DLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lane & 15, kq = lane >> 4;
+    const int tid = threadIdx.x;
     const int m0 = blockIdx.y * DM, n0 = blockIdx.x * DN;
     const int kbeg = blockIdx.z * kchunk;
     const int kend = min(K, kbeg + kchunk);
@@ -140,33 +95,20 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(Mat64 A, Mat64 B, void* _
     for (int j = 0; j < 4; ++j) acc[j] = (f64x4){0.0, 0.0, 0.0, 0.0};
 
     for (int k0 = kbeg; k0 < kend; k0 += DK) {
-        stage_tile<AK>(A, As, m0, M, k0, kend, tid);
-        stage_tile<BK>(B, Bs, n0, N, k0, kend, tid);
+        if (AK) stage_kc(A, As, m0, M, k0, kend, tid);
+        else stage_xc(A, As, m0, M, k0, kend, tid);
+        if (BK) stage_kc(B, Bs, n0, N, k0, kend, tid);
+        else stage_xc(B, Bs, n0, N, k0, kend, tid);
         __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < DK; ks += 4) {
-            const double a = As[ks + kq][wave * 16 + n];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double b = Bs[ks + kq][j * 16 + n];
-                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
-            }
-        }
+        mfma_f64_tile(As, Bs, acc, tid);
         __syncthreads();
     }
-    // D layout (f64 16x16x4): col = lane & 15, row = (lane >> 4) + 4 * i
     const long long zoff = (long long)blockIdx.z * slab_stride;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = m0 + wave * 16 + kq + 4 * i, col = n0 + j * 16 + n;
-            if (row < M && col < N) {
-                const long long o = zoff + (long long)row * ldc + col;
-                if (c_is_f32) reinterpret_cast<float*>(Cp)[o] = (float)acc[j][i];
-                else reinterpret_cast<double*>(Cp)[o] = acc[j][i];
-            }
-        }
+    store_f64_tile(acc, m0, n0, M, N, tid, [&](int row, int col, double v) {
+        const long long o = zoff + (long long)row * ldc + col;
+        if (c_is_f32) reinterpret_cast<float*>(Cp)[o] = (float)v;
+        else reinterpret_cast<double*>(Cp)[o] = v;
+    });
 }
 
 __global__ void slab_reduce64(const double* __restrict__ slabs, int splits, long long slab_stride,
@@ -219,12 +161,6 @@ __device__ inline void jacobi_angle(double alpha, double beta, double gamma, dou
     }
 }
 
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One launch per round; block b owns pair (p, q).  EPT > 0: both columns (m <= 256*EPT) stay in registers
 // between the dot products and the rotation (one pass over W instead of two); EPT == 0: any m, two passes.
 // V == nullptr: the caller does not need the accumulated rotations (eigenvectors of a positive-definite
@@ -257,7 +193,7 @@ __global__ __launch_bounds__(256) void jacobi_round_kernel(double* __restrict__ 
             a += xv * xv; b += yv * yv; g += xv * yv;
         }
     }
-    a = wave_sum(a); b = wave_sum(b); g = wave_sum(g);
+    a = wave_sum_f64(a); b = wave_sum_f64(b); g = wave_sum_f64(g);
     if (lane == 0) { red[0][wave] = a; red[1][wave] = b; red[2][wave] = g; }
     __syncthreads();
     const double alpha = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
@@ -347,7 +283,7 @@ __global__ __launch_bounds__(512) void jacobi_block_kernel(double* __restrict__ 
                     y[e] = i < m ? yc[i] : 0.0;
                     a += x[e] * x[e]; b += y[e] * y[e]; g += x[e] * y[e];
                 }
-                a = wave_sum(a); b = wave_sum(b); g = wave_sum(g);
+                a = wave_sum_f64(a); b = wave_sum_f64(b); g = wave_sum_f64(g);
                 double c, s, rel;
                 jacobi_angle(a, b, g, c, s, rel);
                 offmax = fmax(offmax, rel);
@@ -388,7 +324,7 @@ __global__ __launch_bounds__(512) void jacobi_block_kernel(double* __restrict__ 
                     y[e] = i < m ? qc[i] : 0.0;
                     a += x[e] * x[e]; b += y[e] * y[e]; g += x[e] * y[e];
                 }
-                a = wave_sum(a); b = wave_sum(b); g = wave_sum(g);
+                a = wave_sum_f64(a); b = wave_sum_f64(b); g = wave_sum_f64(g);
                 double c, s, rel;
                 jacobi_angle(a, b, g, c, s, rel);
                 offmax = fmax(offmax, rel);
@@ -772,7 +708,7 @@ static __global__ __launch_bounds__(1024) void lanczos_step_kernel(const double*
     __shared__ double bc;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     auto block_sum = [&](double x) -> double {
-        x = wave_sum(x);
+        x = wave_sum_f64(x);
         __syncthreads();
         if (lane == 0) red[wave] = x;
         __syncthreads();
@@ -815,7 +751,7 @@ static __global__ __launch_bounds__(1024) void lanczos_start_kernel(const double
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double nn = 0.0;
     for (int i = tid; i < n; i += 1024) nn += v0[i] * v0[i];
-    nn = wave_sum(nn);
+    nn = wave_sum_f64(nn);
     if (lane == 0) red[wave] = nn;
     __syncthreads();
     double s = 0.0;

@@ -49,6 +49,13 @@ static inline RowMap to_rowmap(const xps_rowmap* r) {
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// sum of a double over the 64 lanes in a fixed xor butterfly (32, 16, 8, 4, 2, 1): every lane receives the same bits
+__device__ inline double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 __device__ inline float sigmoidf_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // counter-based RNG (splitmix64 finaliser over seed + element-pair index): two 24-bit uniforms per hash

@@ -2,9 +2,9 @@
 //
 //  xps_xcov_grouped_f64    a TABLE of centred cross-moment problems in one launch (+ one reduce launch): per problem
 //                          sum (a - c_a)(b - c_b)^T, sum (a - c_a), sum (b - c_b) and the row count over two lists of
-//                          row blocks.  The tile is gemm_f64_kernel's (xps_align.hip): 64 x 64 outputs per workgroup,
-//                          16 staged rows per step, v_mfma_f64_16x16x4_f64; fp32 / fp64 inputs are converted and centred
-//                          while staged to LDS.  Split-K writes slabs that the reduce adds in slab order: two runs give
+//                          row blocks.  The tile is xps_f64_tile.h's, as in gemm_f64_kernel (xps_align.hip): 64 x 64 outputs
+//                          per workgroup, 16 staged rows per step, fp32 / fp64 inputs converted and centred while staged
+//                          to LDS.  Split-K writes slabs that the reduce adds in slab order: two runs give
 //                          the same bits.
 //  xps_loo_sum_f64         out[f] = sum over g != f of in[g], ascending g, plain adds.
 //  xps_apply_grouped_f64   a table of (X - mean) W products with ragged widths in one launch (xps_apply_f64's arithmetic).
@@ -12,14 +12,10 @@
 //
 // The tables are DEVICE arrays of int64 words built by the caller (alignment/_linalg.py checks every extent against the
 // tensors it was given before it uploads one); the kernels trust them.
-//
-// f64 MFMA operand mapping (16x16x4, lane l: n = l & 15, kq = l >> 4):
-//   A[row n][k kq], B[k kq][col n], D[row = kq + 4*i][col = n] in register i.
 #include "xps_common.h"
+#include "xps_f64_tile.h"
 
 namespace {
-
-constexpr int GM = 64, GN = 64, GK = 16, GLD = 66;     // gemm_f64_kernel's tile: 2 x 16 x 66 doubles = 16.5 KiB of LDS
 
 // words of one xps_xcov_grouped_f64 problem
 enum { XP_A, XP_B, XP_LDA, XP_LDB, XP_A32, XP_B32, XP_CA, XP_CB, XP_BLKA, XP_BLKB, XP_NBLK, XP_BLKLEN, XP_DA, XP_DB,
@@ -32,52 +28,31 @@ static_assert(AP_WORDS_USED <= XPS_APPLY_GROUPED_WORDS, "entry words");
 enum { CS_SRC, CS_ROWLEN, CS_OUT, CS_BEGIN, CS_END, CS_WORDS_USED };
 static_assert(CS_WORDS_USED <= XPS_CND_AVG_FOLDS_WORDS, "segment words");
 
-__device__ inline double ld64(const void* p, int is_f32, long long off) {
-    return is_f32 ? (double)reinterpret_cast<const float*>(p)[off] : reinterpret_cast<const double*>(p)[off];
-}
-
-// Stage S[k][x] = M[row(k0 + k)][x0 + x] - centre[x0 + x] for 16 rows of the problem's block list; rows at or past kend and
-// columns at or past X are zero.  Thread t: row k0 + (t >> 4), columns x0 + 4 (t & 15) .. + 3.
-__device__ inline void stage_rows(const void* M, int is_f32, long long ld, const double* centre, const long long* blk,
-                                  int blk_len, double (*S)[GLD], int x0, int X, int k0, int kend, int tid) {
-    const int k = k0 + (tid >> 4), xb = x0 + (tid & 15) * 4;
-    long long row = 0;
-    if (k < kend) row = blk[k / blk_len] + (k % blk_len);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int x = xb + i;
-        double v = 0.0;
-        if (x < X && k < kend) {
-            v = ld64(M, is_f32, row * ld + x);
-            if (centre) v -= centre[x];
-        }
-        S[tid >> 4][(tid & 15) * 4 + i] = v;
-    }
-}
+// Storage row of contraction index k of a problem: row k % blk_len of block k / blk_len of its list of K / blk_len blocks.
+struct BlockRows {
+    const long long* blk;
+    int blk_len, K;
+    __device__ long long operator()(int k) const { return k < K ? blk[k / blk_len] + (k % blk_len) : 0; }
+};
 
 // One workgroup per (problem, 64-row tile of C, 64-column tile of C, K split); tiles[4 t ..] = {problem, mt, nt, split}.
 // Slab of a split: [C (da x db) | s_a (da) | s_b (db)].
 __global__ __launch_bounds__(256) void xcov_grouped_kernel(const long long* __restrict__ probs, const int* __restrict__ tiles) {
-    __shared__ __attribute__((aligned(16))) double As[GK][GLD];
-    __shared__ __attribute__((aligned(16))) double Bs[GK][GLD];
+    __shared__ __attribute__((aligned(16))) double As[DK][DLD];
+    __shared__ __attribute__((aligned(16))) double Bs[DK][DLD];
     const int* tl = tiles + 4 * (long long)blockIdx.x;
     const long long* P = probs + (long long)tl[0] * XPS_XCOV_GROUPED_WORDS;
     const int mt = tl[1], nt = tl[2], split = tl[3];
-    const void* A = reinterpret_cast<const void*>(P[XP_A]);
-    const void* B = reinterpret_cast<const void*>(P[XP_B]);
-    const long long lda = P[XP_LDA], ldb = P[XP_LDB];
-    const int a32 = (int)P[XP_A32], b32 = (int)P[XP_B32];
-    const double* ca = reinterpret_cast<const double*>(P[XP_CA]);
-    const double* cb = reinterpret_cast<const double*>(P[XP_CB]);
-    const long long* blka = reinterpret_cast<const long long*>(P[XP_BLKA]);
-    const long long* blkb = reinterpret_cast<const long long*>(P[XP_BLKB]);
+    const Mat64 A{reinterpret_cast<const void*>(P[XP_A]), P[XP_LDA], reinterpret_cast<const double*>(P[XP_CA]), (int)P[XP_A32]};
+    const Mat64 B{reinterpret_cast<const void*>(P[XP_B]), P[XP_LDB], reinterpret_cast<const double*>(P[XP_CB]), (int)P[XP_B32]};
     const int blk_len = (int)P[XP_BLKLEN], da = (int)P[XP_DA], db = (int)P[XP_DB];
     const int K = (int)P[XP_NBLK] * blk_len, kchunk = (int)P[XP_KCHUNK];
+    const BlockRows rows_a{reinterpret_cast<const long long*>(P[XP_BLKA]), blk_len, K};
+    const BlockRows rows_b{reinterpret_cast<const long long*>(P[XP_BLKB]), blk_len, K};
     double* slab = reinterpret_cast<double*>(P[XP_SLAB]) + (long long)split * ((long long)da * db + da + db);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lane & 15, kq = lane >> 4;
-    const int m0 = mt * GM, n0 = nt * GN;
+    const int m0 = mt * DM, n0 = nt * DN;
     const int kbeg = split * kchunk;
     const int kend = min(K, kbeg + kchunk);
 
@@ -86,36 +61,21 @@ __global__ __launch_bounds__(256) void xcov_grouped_kernel(const long long* __re
     for (int j = 0; j < 4; ++j) acc[j] = (f64x4){0.0, 0.0, 0.0, 0.0};
     double colsum = 0.0;                       // wave 0: s_a of column m0 + lane (nt == 0); wave 1: s_b of n0 + lane (mt == 0)
 
-    for (int k0 = kbeg; k0 < kend; k0 += GK) {
-        stage_rows(A, a32, lda, ca, blka, blk_len, As, m0, da, k0, kend, tid);
-        stage_rows(B, b32, ldb, cb, blkb, blk_len, Bs, n0, db, k0, kend, tid);
+    for (int k0 = kbeg; k0 < kend; k0 += DK) {
+        stage_xc(A, As, m0, da, k0, kend, tid, rows_a);
+        stage_xc(B, Bs, n0, db, k0, kend, tid, rows_b);
         __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < GK; ks += 4) {
-            const double a = As[ks + kq][wave * 16 + n];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double b = Bs[ks + kq][j * 16 + n];
-                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
-            }
-        }
+        mfma_f64_tile(As, Bs, acc, tid);
         if (wave == 0 && nt == 0) {
 #pragma unroll
-            for (int k = 0; k < GK; ++k) colsum += As[k][lane];
+            for (int k = 0; k < DK; ++k) colsum += As[k][lane];
         } else if (wave == 1 && mt == 0) {
 #pragma unroll
-            for (int k = 0; k < GK; ++k) colsum += Bs[k][lane];
+            for (int k = 0; k < DK; ++k) colsum += Bs[k][lane];
         }
         __syncthreads();
     }
-    // D layout (f64 16x16x4): col = lane & 15, row = (lane >> 4) + 4 * i
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = m0 + wave * 16 + kq + 4 * i, col = n0 + j * 16 + n;
-            if (row < da && col < db) slab[(long long)row * db + col] = acc[j][i];
-        }
+    store_f64_tile(acc, m0, n0, da, db, tid, [&](int row, int col, double v) { slab[(long long)row * db + col] = v; });
     if (wave == 0 && nt == 0 && m0 + lane < da) slab[(long long)da * db + m0 + lane] = colsum;
     if (wave == 1 && mt == 0 && n0 + lane < db) slab[(long long)da * db + da + n0 + lane] = colsum;
 }
@@ -145,77 +105,37 @@ __global__ void loo_sum_kernel(const double* __restrict__ in, double* __restrict
     out[(long long)f * len + e] = s;
 }
 
-// Stage S[k][x] = X[x0 + x][k0 + k] - mean[k0 + k] (X stored row-major, k contiguous): stage_tile<true> of xps_align.hip.
-__device__ inline void stage_x(const void* X, int is_f32, long long ld, const double* mean, double (*S)[GLD], int x0, int rows,
-                               int k0, int kend, int tid) {
-    const int x = x0 + (tid >> 2), kb = k0 + (tid & 3) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = kb + i;
-        double v = 0.0;
-        if (x < rows && k < kend) {
-            v = ld64(X, is_f32, (long long)x * ld + k);
-            if (mean) v -= mean[k];
-        }
-        S[(tid & 3) * 4 + i][tid >> 2] = v;
-    }
-}
-__device__ inline void stage_w(const double* W, long long ld, double (*S)[GLD], int x0, int X, int k0, int kend, int tid) {
-    const int k = k0 + (tid >> 4), xb = x0 + (tid & 15) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int x = xb + i;
-        S[tid >> 4][(tid & 15) * 4 + i] = (x < X && k < kend) ? W[(long long)k * ld + x] : 0.0;
-    }
-}
-
 // One workgroup per (entry, 64-row tile, 64-column tile); tiles[3 t ..] = {entry, mt, nt}.
 __global__ __launch_bounds__(256) void apply_grouped_kernel(const long long* __restrict__ ents, const int* __restrict__ tiles) {
-    __shared__ __attribute__((aligned(16))) double As[GK][GLD];
-    __shared__ __attribute__((aligned(16))) double Bs[GK][GLD];
+    __shared__ __attribute__((aligned(16))) double As[DK][DLD];
+    __shared__ __attribute__((aligned(16))) double Bs[DK][DLD];
     const int* tl = tiles + 3 * (long long)blockIdx.x;
     const long long* E = ents + (long long)tl[0] * XPS_APPLY_GROUPED_WORDS;
-    const void* X = reinterpret_cast<const void*>(E[AP_X]);
-    const int x32 = (int)E[AP_X32], rows = (int)E[AP_ROWS], d_in = (int)E[AP_DIN], d_out = (int)E[AP_DOUT];
-    const long long ldx = E[AP_LDX], ldw = E[AP_LDW], ldo = E[AP_LDO];
-    const double* mean = reinterpret_cast<const double*>(E[AP_MEAN]);
-    const double* W = reinterpret_cast<const double*>(E[AP_W]);
+    const Mat64 X{reinterpret_cast<const void*>(E[AP_X]), E[AP_LDX], reinterpret_cast<const double*>(E[AP_MEAN]), (int)E[AP_X32]};
+    const Mat64 W{reinterpret_cast<const void*>(E[AP_W]), E[AP_LDW], nullptr, 0};
+    const int rows = (int)E[AP_ROWS], d_in = (int)E[AP_DIN], d_out = (int)E[AP_DOUT];
+    const long long ldo = E[AP_LDO];
     void* out = reinterpret_cast<void*>(E[AP_OUT]);
     const int o32 = (int)E[AP_O32];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lane & 15, kq = lane >> 4;
-    const int m0 = tl[1] * GM, n0 = tl[2] * GN;
+    const int tid = threadIdx.x;
+    const int m0 = tl[1] * DM, n0 = tl[2] * DN;
 
     f64x4 acc[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] = (f64x4){0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < d_in; k0 += GK) {
-        stage_x(X, x32, ldx, mean, As, m0, rows, k0, d_in, tid);
-        stage_w(W, ldw, Bs, n0, d_out, k0, d_in, tid);
+    for (int k0 = 0; k0 < d_in; k0 += DK) {
+        stage_kc(X, As, m0, rows, k0, d_in, tid);
+        stage_xc(W, Bs, n0, d_out, k0, d_in, tid);
         __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < GK; ks += 4) {
-            const double a = As[ks + kq][wave * 16 + n];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double b = Bs[ks + kq][j * 16 + n];
-                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
-            }
-        }
+        mfma_f64_tile(As, Bs, acc, tid);
         __syncthreads();
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = m0 + wave * 16 + kq + 4 * i, col = n0 + j * 16 + n;
-            if (row < rows && col < d_out) {
-                const long long o = (long long)row * ldo + col;
-                if (o32) reinterpret_cast<float*>(out)[o] = (float)acc[j][i];
-                else reinterpret_cast<double*>(out)[o] = acc[j][i];
-            }
-        }
+    store_f64_tile(acc, m0, n0, rows, d_out, tid, [&](int row, int col, double v) {
+        const long long o = (long long)row * ldo + col;
+        if (o32) reinterpret_cast<float*>(out)[o] = (float)v;
+        else reinterpret_cast<double*>(out)[o] = v;
+    });
 }
 
 __global__ void cnd_avg_folds_kernel(const long long* __restrict__ segs, const int* __restrict__ trials) {

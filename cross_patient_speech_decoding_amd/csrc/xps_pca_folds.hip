@@ -30,13 +30,6 @@ constexpr int PK_T = 16, PK_K = 32;  // xps_prefix_kernels_f64: 16 x 16 outputs 
 enum { PK_Z, PK_LDZ, PK_N, PK_R, PK_CUT0, PK_CUT1, PK_WORDS_USED };
 static_assert(PK_WORDS_USED <= XPS_PREFIX_KERNELS_WORDS, "problem words");
 
-// sum over the wave of v in a fixed order (every lane receives the same bits)
-__device__ inline double wave_sum_fixed(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
-
 // flag[0] = 1 if an index of the list lies outside [0, N)
 __global__ void gc_check_rows_kernel(const int* __restrict__ rows, long long total, int N, long long* flag) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -55,7 +48,7 @@ __global__ __launch_bounds__(256) void gc_row_mean_kernel(const double* __restri
     const double* g = G + (long long)rows[off + a] * ldg;
     double s = 0.0;
     for (int t = lane; t < n_tr; t += 64) s += g[rows[off + t]];
-    s = wave_sum_fixed(s);
+    s = wave_sum_f64(s);
     if (lane == 0) m[off + a] = s / (double)n_tr;
 }
 
@@ -72,7 +65,7 @@ __global__ __launch_bounds__(256) void gc_center_kernel(const double* __restrict
     if (threadIdx.x < 64) {
         double s = 0.0;
         for (int b = threadIdx.x; b < n_tr; b += 64) s += m[off + b];
-        s = wave_sum_fixed(s);
+        s = wave_sum_f64(s);
         if (threadIdx.x == 0) mm_s = s / (double)n_tr;
     }
     __syncthreads();

@@ -264,7 +264,7 @@ def build_plan_pca(estimator, split_candidates, X, yi, classes, splits):
     eig = [None] * nf
     for size in sorted(set(n_tr)):                              # stacked by size: folds differ in size by one
         fs = [f for f in range(nf) if n_tr[f] == size]
-        for f, res in zip(fs, LA.eigh_psd_stack(np.stack([0.5 * (blocks[f] + blocks[f].T) for f in fs]))):
+        for f, res in zip(fs, LA.eigh_psd_batched(np.stack([0.5 * (blocks[f] + blocks[f].T) for f in fs]))):
             eig[f] = res
     plan = Plan()
     ncs = [b.get('n_components', red.n_components) for b, _ in split_candidates]

@@ -7,6 +7,7 @@ import numpy as np
 from sklearn.base import BaseEstimator, TransformerMixin
 
 from ..alignment import _linalg as LA
+from ..alignment.pca import sign_rule
 
 
 class NoCenterPCA(BaseEstimator, TransformerMixin):
@@ -18,10 +19,7 @@ class NoCenterPCA(BaseEstimator, TransformerMixin):
         Xd = LA.to_device(X)
         w, V = LA.eigh_psd(LA.xcov(Xd))                     # w = S**2, V columns = right singular vectors
         w = np.clip(w, 0.0, None)
-        idx = np.argmax(np.abs(V), axis=0)
-        signs = np.sign(V[idx, np.arange(V.shape[1])])
-        signs[signs == 0] = 1
-        V = V * signs
+        V = V * sign_rule(V, 0)
         k = self._get_components(X, np.sqrt(w))
         self.components_ = V[:, :k]
         self.explained_variance_ = w[:min(X.shape)]

@@ -5,6 +5,7 @@ import pytest
 from sklearn.model_selection import KFold, StratifiedKFold
 
 from cross_patient_speech_decoding_amd.alignment import fold_plan, label2str
+from cross_patient_speech_decoding_amd.alignment.AlignCCA import cca_tail
 from cross_patient_speech_decoding_amd.utils.synthetic import make_patient
 
 
@@ -120,3 +121,27 @@ def test_train_that_is_not_the_complement_raises():
             fold_plan(y, pool, bad)
     with pytest.raises(ValueError, match='outside range'):
         fold_plan(y, pool, [(splits[0][0], np.array([60]))])
+
+
+@pytest.mark.parametrize('shape,top', [((5, 3), 0.9), ((3, 5), 0.9), ((4, 4), 1.0 + 1e-9)])
+def test_the_cca_tail_equals_its_line_by_line_restatement(shape, top):
+    """M_a, M_b and the clipped S of ``AlignCCA.cca_tail`` (the end of ``_cca_device`` and of the fold-batched ``_solve_cca``) on a
+    tall and a wide K, and on a K whose largest computed singular value lies above 1."""
+    rng = np.random.default_rng(shape[0] * 10 + shape[1])
+    K = rng.standard_normal(shape)
+    K *= top / np.linalg.norm(K, 2)
+    U, S, Vt = np.linalg.svd(K, full_matrices=False)
+    W_a, W_b = rng.standard_normal((7, shape[0])), rng.standard_normal((6, shape[1]))
+    M_a, M_b, S_out = cca_tail(W_a, W_b, U, S, Vt)
+    d = min(K.shape)
+    np.testing.assert_array_equal(M_a, W_a @ U[:, :d])
+    np.testing.assert_array_equal(M_b, W_b @ Vt.T[:, :d])
+    ref = S[:d].copy()
+    ref[ref < 0] = 0
+    ref[ref >= 1] = 1
+    np.testing.assert_array_equal(S_out, ref)
+    assert M_a.shape == (7, d) and M_b.shape == (6, d) and S_out.shape == (d,) and S_out is not S
+    if top > 1:
+        assert S[0] > 1 and S_out[0] == 1.0 and (S_out[1:] == S[1:d]).all()      # clipped; the input is not touched
+    else:
+        assert (S_out == S[:d]).all() and 0 < S_out.min() and S_out.max() < 1

@@ -232,6 +232,7 @@ def test_xcov_grouped_against_numpy_and_bit_identical():
         (M17, M33, [], [], 20, c17, c33),                                 # zero blocks
         (M17, M17, long_blocks, long_blocks[::-1].copy(), 20, c17, None), # long: the split-K route
         (wide[:, :33], M130, [0, 60, 30], [3, 77, 40], 7, c33, c130),      # strided rows, block length 7, 33 x 130
+        (M130, M130, [0, 20, 40, 60, 80], [0, 20, 40, 60, 80], 20, c130, c130),   # rows 0..99 in order, one split: = xps_xcov_f64
     ]
     dev_m = {id(m): _dev(m) for m in (M17, M33, M130)}
     wide_d = _dev(wide)
@@ -256,6 +257,10 @@ def test_xcov_grouped_against_numpy_and_bit_identical():
         assert np.abs(blk[da * db + da:-1] - sb).max() <= 1e-12 * s_scale, i
         if cnt == 0:
             assert not blk.any()
+    # the whole matrix in order as one problem = xps_xcov_f64, bit for bit (the same 16-row steps over the same rows, one split)
+    c130_d = _dev(c130)
+    whole = la.xcov(dev_m[id(M130)], dev_m[id(M130)], c130_d, c130_d).cpu().numpy()
+    np.testing.assert_array_equal(out[offs[6]:offs[6] + 130 * 130].reshape(130, 130), whole)
     with pytest.raises(ValueError, match='outside its matrix'):
         la.xcov_grouped([(dev_m[id(M17)], dev_m[id(M33)], [290], [0], 20, None, None)])
 

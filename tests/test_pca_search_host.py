@@ -88,6 +88,18 @@ def test_the_component_count_rule_is_one_function():
     np.testing.assert_array_equal(P.gram_ratio([0.0, 0.0], 2, 5), [0.0, 0.0])
 
 
+def test_the_sign_rule_is_one_function():
+    #             largest |.| negative   exact tie: first wins   all zero
+    M = np.array([[1.0,                  -2.0,                   0.0],
+                  [-3.0,                 2.0,                    0.0],
+                  [2.0,                  -2.0,                   0.0]])
+    np.testing.assert_array_equal(P.sign_rule(M, 0), [-1.0, -1.0, 1.0])          # down the columns
+    np.testing.assert_array_equal(P.sign_rule(M.T.copy(), 1), [-1.0, -1.0, 1.0])   # the same vectors as rows
+    np.testing.assert_array_equal(P.sign_rule(np.array([[2.0, -2.0, 1.0]]), 1), [1.0])     # the tie the other way round
+    signed = M * P.sign_rule(M, 0)
+    assert signed[1, 0] == 3.0 and signed[0, 1] == 2.0 and not signed[:, 2].any()
+
+
 def test_keys_are_split_with_n_components_batched_and_everything_else_refused():
     pipe = make_pipeline(DimRedReshape(A.PCA), SVC(kernel='rbf'))
     got = S.split_params_pca(pipe, {'svc__C': 5, 'svc__gamma': 0.2, 'dimredreshape__n_components': 0.9})
