@@ -157,6 +157,12 @@ def apply(X, W, mean=None, out_f32=False):
 
 
 # ------------------------------------------------------------------------------------ k3 / k5
+def _jacobi_tol(m_rows, n_cols):
+    """Converged = every pair orthogonal to rounding level; the largest |cos| over n^2/2 pairs of length-m columns cannot
+    be pushed below a few eps * sqrt(m), so the bound grows slowly with the size."""
+    return max(1e-14, 4.0 * EPS * np.sqrt(max(m_rows, n_cols)) * np.log2(max(n_cols, 2)))
+
+
 def _jacobi(Wc, n_cols, m_rows, max_sweeps=40, tol=None, want_v=True):
     """Wc: (n_cols, m_rows) float64 device tensor = column-major (m x n) matrix.  Rotates in place;
     returns V (n_cols x n_cols as rows = columns of V, i.e. V^T in row-major terms), or None when
@@ -165,9 +171,7 @@ def _jacobi(Wc, n_cols, m_rows, max_sweeps=40, tol=None, want_v=True):
     Small problems (n <= 128 and the matrix within one workgroup's LDS) are decomposed by ONE launch that
     runs every sweep and the convergence test on the device; larger ones by one launch per round."""
     if tol is None:
-        # converged = every pair orthogonal to rounding level; the largest |cos| over n^2/2 pairs of length-m
-        # columns cannot be pushed below a few eps * sqrt(m), so the bound grows slowly with the size
-        tol = max(1e-14, 4.0 * EPS * np.sqrt(max(m_rows, n_cols)) * np.log2(max(n_cols, 2)))
+        tol = _jacobi_tol(m_rows, n_cols)
     Vc = torch.empty(n_cols, n_cols, dtype=F64, device=Wc.device) if want_v else None
     if lib().xps_jacobi_small_supported(m_rows, n_cols, int(want_v)):
         call('xps_jacobi_small_f64', Wc.data_ptr(), Wc.stride(0), 0, ptr(Vc), n_cols, 0,
@@ -192,13 +196,85 @@ def jacobi_batched(Wb, want_v=True, max_sweeps=40, tol=None):
     launch (one workgroup per matrix).  Returns Vb (batch, n, n) or None."""
     batch, n, m = Wb.shape
     if tol is None:
-        tol = max(1e-14, 4.0 * EPS * np.sqrt(max(m, n)) * np.log2(max(n, 2)))
+        tol = _jacobi_tol(m, n)
     if not lib().xps_jacobi_small_supported(m, n, int(want_v)):
         raise ValueError(f'jacobi_batched: {m} x {n} does not fit the single-workgroup kernel')
     Vb = torch.empty(batch, n, n, dtype=F64, device=Wb.device) if want_v else None
     call('xps_jacobi_small_f64', Wb.data_ptr(), Wb.stride(1), Wb.stride(0), ptr(Vb), n,
          n * n, m, n, batch, max_sweeps, tol, None, None, stream())
     return Vb
+
+
+RAGGED_GROUP = 4        # single sweeps enqueued blind between two downloads of `frozen` (DESIGN.md section 4.18)
+_PACK_ALIGN = 64        # doubles: every packed matrix starts on a 512-byte boundary (the kernel's column loads start aligned)
+
+
+def _packed_offsets(lengths):
+    """Element offsets (and, last, the total) of buffers of `lengths` doubles packed one after another, each aligned."""
+    offs = [0]
+    for ln in lengths:
+        offs.append(offs[-1] + -(-int(ln) // _PACK_ALIGN) * _PACK_ALIGN)
+    return offs
+
+
+def _jacobi_ragged_packed(buf, offs, shapes, max_sweeps=40, tol=None):
+    """The driver of jacobi_ragged on matrices already inside the flat float64 device buffer `buf`: matrix b is column-major
+    m x n with leading dimension ld at element offs[b], shapes[b] = (m, n, ld).  Rotates in place; returns the sweeps each
+    matrix ran (int32 ndarray)."""
+    batch = len(shapes)
+    if batch == 0:
+        return np.zeros(0, dtype=np.int32)
+    w_off = np.asarray(offs, dtype=np.int64)
+    ms, ns, lds = (np.asarray([sh[k] for sh in shapes], dtype=dt) for k, dt in ((0, np.int32), (1, np.int32), (2, np.int64)))
+    tols = np.array([_jacobi_tol(m, n) for m, n in zip(ms, ns)] if tol is None else np.broadcast_to(tol, (batch,)),
+                    dtype=np.float64)
+    dev = buf.device
+    tol_d = torch.from_numpy(tols).to(dev)
+    off_d = torch.zeros(batch, dtype=F64, device=dev)
+    state = torch.zeros(2, batch, dtype=torch.int32, device=dev)              # frozen | sweeps_done
+    nb = int(lib().xps_jacobi_sweeps_batched_f64_workspace(batch))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=dev)
+
+    def sweeps(k):
+        call('xps_jacobi_sweeps_batched_f64', buf.data_ptr(), buf.numel(), w_off.ctypes.data, lds.ctypes.data, ms.ctypes.data,
+             ns.ctypes.data, batch, k, 1, tol_d.data_ptr(), off_d.data_ptr(), state[0].data_ptr(), state[1].data_ptr(),
+             ws.data_ptr(), nb, stream())
+
+    # _jacobi's schedule per matrix -- 5 sweeps, then 1 at a time, checked after every call -- with the checks on the device:
+    # a matrix freezes at the sweep where _jacobi would have stopped it, and `frozen` comes down once per group of calls
+    done = 0
+    if max_sweeps > 0:
+        sweeps(5)
+        done = 5
+    while done < max_sweeps:
+        k = min(max(RAGGED_GROUP, 1), max_sweeps - done)
+        for _ in range(k):
+            sweeps(1)
+        done += k
+        if bool(state[0].cpu().numpy().all()):
+            break
+    return state[1].cpu().numpy()
+
+
+def jacobi_ragged(mats, max_sweeps=40, tol=None):
+    """One-sided Jacobi (no V) of a RAGGED batch: mats is a list of 2-D float64 device tensors, mats[b] of shape (n_b, m_b) a
+    column-major m_b x n_b matrix with xps_jacobi_batched_supported(m_b, n_b).  The matrices are packed into one device
+    buffer and every sweep covers the whole batch (one launch per block round); each matrix stops at the sweep where _jacobi
+    would have stopped it alone, with the same bits.  The number of host synchronisations depends on the sweeps the slowest
+    matrix needs, not on the batch.  ``tol``: None (per matrix, _jacobi's formula), a scalar or one value per matrix.
+    Returns (rotated, sweeps_done): views into the packed buffer and an int32 ndarray."""
+    for t in mats:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 and t.dtype == F64):
+            raise ValueError('jacobi_ragged: 2-D float64 device matrices are needed')
+        if not lib().xps_jacobi_batched_supported(t.shape[1], t.shape[0]):
+            raise ValueError(f'jacobi_ragged: {t.shape[1]} x {t.shape[0]} is not a shape of the block kernel')
+    offs = _packed_offsets([t.numel() for t in mats])
+    buf = torch.empty(int(offs[-1]), dtype=F64, device=device())
+    views = [buf[o:o + t.numel()].view(t.shape) for o, t in zip(offs, mats)]
+    for v, t in zip(views, mats):
+        v.copy_(t)
+    done = _jacobi_ragged_packed(buf, offs[:-1], [(t.shape[1], t.shape[0], t.shape[1]) for t in mats], max_sweeps, tol)
+    return views, done
 
 
 def chol_whiten_blocks(Gd, offs, scale, shift, LHS=None):
@@ -313,18 +389,97 @@ def _shifted_stack(Cs, well_conditioned):
     return Wb, sig
 
 
-def eigh_psd_batched(Cs, well_conditioned=False):
-    """eigh_psd of equally sized small PSD matrices by ONE Jacobi launch and one download: a list of (w descending, V).  Cs is a
-    (batch, n, n) float64 ndarray or a list of matrices (ndarrays or device tensors).  Matrices of different sizes, or of a size
-    beyond the one-workgroup kernel, are decomposed one at a time."""
+def route_sizes(sizes, small_ok, ragged_ok):
+    """Where eigh_psd_batched sends square matrices of the orders `sizes` (pure numpy: no device): ``(small, ragged, alone)``
+    with `small` a dict order -> indices for one jacobi_batched launch each (orders with small_ok(n)), `ragged` the indices
+    of the ONE jacobi_ragged call (ragged_ok(n)) and `alone` the indices that eigh_psd takes one at a time.  Indices ascend."""
+    small, ragged, alone = {}, [], []
+    for i, n in enumerate(sizes):
+        if small_ok(int(n)):
+            small.setdefault(int(n), []).append(i)
+        elif ragged_ok(int(n)):
+            ragged.append(i)
+        else:
+            alone.append(i)
+    return small, ragged, alone
+
+
+def _shifts_of(mats, well_conditioned):
+    """_shift_of of every device matrix of `mats` -- the same torch expression per matrix, so the same bits -- with ONE
+    download for all of them."""
+    if well_conditioned or not mats:
+        return [0.0] * len(mats)
+    g = torch.stack([C.abs().sum(dim=-1).max() for C in mats]).cpu().numpy()
+    return [float(x) * _SHIFT if float(x) > 0 else 1.0 for x in g]
+
+
+def _small_stack(Cs, idx, well_conditioned):
+    """(Wb, sig) of the matrices Cs[i], i in idx -- one size of the one-workgroup kernel.  ndarrays, in a stack or in a list,
+    are shifted on the host as an ndarray stack is (one rule, whether or not the batch has other sizes in it); a list of one
+    shape that holds device matrices as _shifted_stack shifts it; device matrices out of a list of mixed sizes as eigh_psd
+    shifts each of them alone."""
+    if all(isinstance(Cs[i], np.ndarray) for i in idx):
+        return _shifted_stack(np.stack([np.asarray(Cs[i], dtype=np.float64) for i in idx]), well_conditioned)
+    if len(idx) == len(Cs):
+        return _shifted_stack(Cs, well_conditioned)
+    mats = [to_device(Cs[i]).to(F64) for i in idx]
+    sig = _shifts_of(mats, well_conditioned)
+    Wb = torch.stack(mats).contiguous()
+    for W, sg in zip(Wb, sig):
+        if sg:
+            W.diagonal().add_(sg)
+    return Wb, sig
+
+
+def _eigh_ragged(Cs, idx, well_conditioned):
+    """_eig_from_w results (None where rejected) of the matrices Cs[i], i in idx, through ONE jacobi_ragged call.  Every
+    matrix is what eigh_psd would have worked on, bit for bit: its shift is eigh_psd's torch expression evaluated per matrix
+    on the device; the scalars of the whole batch come down in one download."""
+    ns = [int(Cs[i].shape[0]) for i in idx]
+    offs = _packed_offsets([n * n for n in ns])
+    if isinstance(Cs, np.ndarray) or all(isinstance(Cs[i], np.ndarray) for i in idx):
+        host = np.zeros(int(offs[-1]))
+        for o, n, i in zip(offs, ns, idx):
+            host[o:o + n * n] = np.asarray(Cs[i], dtype=np.float64).reshape(-1)
+        buf = to_device(host)                                              # one upload
+        views = [buf[o:o + n * n].view(n, n) for o, n in zip(offs, ns)]
+        seen = views
+    else:
+        buf = torch.empty(int(offs[-1]), dtype=F64, device=device())
+        views = [buf[o:o + n * n].view(n, n) for o, n in zip(offs, ns)]
+        seen = [to_device(Cs[i]).to(F64) for i in idx]                     # what eigh_psd takes its shift from
+        for v, c in zip(views, seen):
+            v.copy_(c)
+    sig = _shifts_of(seen, well_conditioned)
+    for v, sg in zip(views, sig):
+        if sg:
+            v.diagonal().add_(sg)
+    _jacobi_ragged_packed(buf, offs[:-1], [(n, n, n) for n in ns])
+    host = buf.cpu().numpy()
+    return [_eig_from_w(host[o:o + n * n].reshape(n, n), sg) for o, n, sg in zip(offs, ns, sig)]
+
+
+def eigh_psd_batched(Cs, well_conditioned=False, one_at_a_time=False):
+    """eigh_psd of a batch of PSD matrices of any mix of sizes: a list of (w descending, V) in input order.  Cs is a
+    (batch, n, n) float64 ndarray or a list of matrices (ndarrays or device tensors).  Sizes of the one-workgroup kernel take
+    ONE jacobi_batched launch and one download per distinct size; sizes of the block kernel (up to 1024) take ONE jacobi_ragged
+    call together -- a fixed number of host synchronisations, whatever the batch; anything larger goes through eigh_psd.  A
+    matrix that is not PSD beyond its shift falls back to eigh_psd on its own.  ``one_at_a_time``: every matrix beyond the
+    one-workgroup kernel goes through eigh_psd instead; the results are the same bit for bit."""
     if isinstance(Cs, np.ndarray):
         Cs = np.ascontiguousarray(Cs, dtype=np.float64)
-    n = Cs[0].shape[0]
-    if len({tuple(c.shape) for c in Cs}) != 1 or not lib().xps_jacobi_small_supported(n, n, 0):
-        return [eigh_psd(to_device(c), well_conditioned) for c in Cs]
-    Wb, sig = _shifted_stack(Cs, well_conditioned)
-    jacobi_batched(Wb, want_v=False)
-    res = [_eig_from_w(W, sg) for W, sg in zip(Wb.cpu().numpy(), sig)]
+    L = lib()
+    small, ragged, _ = route_sizes([c.shape[0] for c in Cs], lambda n: bool(L.xps_jacobi_small_supported(n, n, 0)),
+                                   lambda n: not one_at_a_time and bool(L.xps_jacobi_batched_supported(n, n)))
+    res = [None] * len(Cs)
+    for idx in small.values():
+        Wb, sig = _small_stack(Cs, idx, well_conditioned)
+        jacobi_batched(Wb, want_v=False)
+        for i, W, sg in zip(idx, Wb.cpu().numpy(), sig):
+            res[i] = _eig_from_w(W, sg)
+    if ragged:
+        for i, r in zip(ragged, _eigh_ragged(Cs, ragged, well_conditioned)):
+            res[i] = r
     return [r if r is not None else eigh_psd(to_device(Cs[i]), well_conditioned) for i, r in enumerate(res)]
 
 

@@ -12,11 +12,11 @@ whose test sets partition the trials (KFold / StratifiedKFold) all of that is sh
 
 Launch list of one ``fit_folds`` (k folds, P pooled patients; no Python loop over folds issues device calls except the
 Jacobi launches -- one per distinct matrix size -- and the chunks of ``max_bytes``):
-  per pooled patient (once)   PCA (colsum, xcov, Jacobi), transform, condition means       existing kernels
+  per pooled patient (once)   PCA (colsum, xcov; ONE Jacobi call for all patients), transform, condition means
   1  xps_colsum_f64           provisional centre
   2  xps_xcov_grouped_f64     group moments, one problem per trial group
   3  xps_loo_sum_f64          fold sums
-  4  Jacobi                   k fold covariances in one launch (one at a time above 128 channels)
+  4  Jacobi                   k fold covariances in one launch (above 128 channels: one ragged batch)
   5  xps_apply_grouped_f64    Z_f for every fold + the training rows of every fold's pooled tensor (float32)
   6  xps_cnd_avg_folds_f64    every fold's condition means
   7  xps_xcov_grouped_f64     C_aa, C_bb, C_ab of every (fold, patient)
@@ -32,7 +32,7 @@ import torch
 from . import _linalg as LA
 from .AlignCCA import _cca_device, cca_tail
 from .alignment_utils import _cnd_avg_device, label2str
-from .pca import PCA, count_components, sign_rule
+from .pca import count_components, fit_many, sign_rule
 
 SPECTRUM_LIMIT = 1e10          # above it rank_from_gram_eigs and LAPACK's rank rule may disagree: the problem takes _cca_device
 
@@ -207,11 +207,13 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
 
     # pooled patients: PCA and condition means once
     Zp, Bp, pool_n = [], [], []
-    for (x, _, ya), pk in zip(pool_data, plan.pool_keys):
-        xd = LA.to_device(x)
+    pool_d = [LA.to_device(x) for x, _, _ in pool_data]
+    for xd in pool_d:
         if xd.dim() != 3 or xd.shape[1] != T:
             raise ValueError('fit_folds: every pooled patient must be (trials, T, channels) with the target\'s T')
-        z = PCA(n_components=n_components).fit(xd.reshape(-1, xd.shape[-1])).transform_device(xd)
+    pool_pca = fit_many([xd.reshape(-1, xd.shape[-1]) for xd in pool_d], n_components=n_components)
+    for xd, pca, (_, _, ya), pk in zip(pool_d, pool_pca, pool_data, plan.pool_keys):
+        z = pca.transform_device(xd)
         uniq, b = _cnd_avg_device(z, label2str(_np(ya)))
         assert np.array_equal(uniq, pk)
         Zp.append(z.reshape(-1, z.shape[-1]))

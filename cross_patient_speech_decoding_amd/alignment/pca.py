@@ -74,7 +74,11 @@ class PCA:
         if self.solver == 'gram' or (self.solver == 'auto' and d > n):
             return self._fit_gram(Xd, mean)
         cov = LA.xcov(Xd, None, mean) / (n - 1)
-        w, V = LA.eigh_psd(cov)
+        return self._fit_from_eig(LA.eigh_psd(cov), mean, n, d)
+
+    def _fit_from_eig(self, eig, mean, n, d):
+        """The covariance solver's tail: (w, V) of the covariance of n rows of d features -> the fitted attributes."""
+        w, V = eig
         w = np.clip(w, 0.0, None)
         comps = V.T.copy()
         total = w.sum()
@@ -131,6 +135,27 @@ class PCA:
         Zd = LA.to_device(Z)
         W = LA.to_device(np.ascontiguousarray(self.components_))
         return (LA.apply(Zd, W) + self._mean_d).cpu().numpy()
+
+
+def fit_many(Xs, n_components=None, solver='covariance'):
+    """``PCA(n_components).fit(x)`` for every x of Xs -- inputs of any mix of widths -- with ONE eigh_psd_batched call over all
+    the covariances: column mean and covariance per input as in ``PCA.fit``, then widths of the one-workgroup Jacobi share one
+    launch per width and the wider ones share one ragged call.  Returns the fitted ``PCA`` objects, attribute for attribute
+    what the separate fits give, bit for bit.  Only the covariance solver is batched."""
+    if solver != 'covariance':
+        raise ValueError(f"fit_many batches the covariance solver only; got solver={solver!r}")
+    models, means, covs, shapes = [], [], [], []
+    for x in Xs:
+        Xd = LA.to_device(x)
+        Xd = Xd.reshape(-1, Xd.shape[-1])
+        n, d = Xd.shape
+        mean = LA.col_mean(Xd)
+        means.append(mean)
+        covs.append(LA.xcov(Xd, None, mean) / (n - 1))
+        shapes.append((n, d))
+        models.append(PCA(n_components=n_components, solver=solver))
+    eigs = LA.eigh_psd_batched(covs) if covs else []
+    return [m._fit_from_eig(e, mean, n, d) for m, e, mean, (n, d) in zip(models, eigs, means, shapes)]
 
 
 class GramPCA(PCA):

@@ -238,11 +238,34 @@ __global__ __launch_bounds__(256) void jacobi_round_kernel(double* __restrict__ 
 // n/JB - 1 launches per sweep instead of n - 1.  The pairs INSIDE a block are rotated by one extra launch per
 // sweep (WITHIN mode: blocks 2j and 2j+1, round-robin over the 8 columns of each).  Every pair is visited exactly
 // once per sweep, so the sweep counts are those of the cyclic orderings.
+//
+// Ragged batch (xps_jacobi_sweeps_batched_f64): `tab` holds device tables with one entry per matrix, indexed by blockIdx.y
+// (tab.off == nullptr: one matrix, described by the arguments).  The kernel's first statements replace W, ldw, m, n and nb
+// by the entry of its matrix; nothing after them differs, so a matrix's iterates in a batch are its iterates alone, bit
+// for bit.  The grid is sized for the largest nb of the batch: a matrix with a smaller nb has nothing in block columns
+// >= nb / 2 nor in rounds >= nb - 1 (rr_pair with its own nb would revisit pairs there), and a frozen matrix (converged at
+// an earlier check) is left untouched.
 constexpr int JB = 8, JB_MAXM = 1024, JB_EPL = JB_MAXM / 64;
+__host__ __device__ inline int jacobi_block_count(int n) { return ((n + JB - 1) / JB + 1) & ~1; }   // padded to an even count
+struct JacobiBatch {
+    const long long* off;                                  // first element of each matrix in the batch's buffer
+    const long long* ldw;
+    const int* m;
+    const int* n;
+    const int* frozen;                                     // != 0: the matrix converged at an earlier check
+};
 template <bool CROSS>
 __global__ __launch_bounds__(512) void jacobi_block_kernel(double* __restrict__ W, long long ldw, int m, int n, int nb,
-                                                           int round, unsigned long long* __restrict__ off_bits) {
+                                                           int round, unsigned long long* __restrict__ off_bits,
+                                                           const JacobiBatch tab) {
     extern __shared__ double jcols[];                      // [2 * JB][m]
+    if (tab.off) {
+        const int b = blockIdx.y;
+        n = tab.n[b]; nb = jacobi_block_count(n);
+        if (tab.frozen[b] || (int)blockIdx.x >= nb / 2 || (CROSS && round >= nb - 1)) return;
+        W += tab.off[b]; ldw = tab.ldw[b]; m = tab.m[b];
+        if (off_bits) off_bits += b;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int I, J;
     if (CROSS) rr_pair(nb, round, blockIdx.x, I, J);
@@ -352,6 +375,23 @@ __global__ __launch_bounds__(512) void jacobi_block_kernel(double* __restrict__ 
         }
     }
     if (off_bits && lane == 0 && offmax > 0.0) atomicMax(off_bits, (unsigned long long)__double_as_longlong(offmax));
+}
+
+// Before the last sweep of a batched call: off[b] = 0 for the matrices that run.
+__global__ void jacobi_batch_begin_kernel(double* __restrict__ off, const int* __restrict__ frozen, int batch) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < batch && !frozen[b]) off[b] = 0.0;
+}
+
+// After the last sweep of a checked batched call (ONE block; the only writer of `frozen`, ordered between sweeps by the
+// stream): the matrices that ran count their sweeps and freeze where the sweep's largest |cos| is within their tolerance.
+__global__ void jacobi_batch_check_kernel(const double* __restrict__ tol, const double* __restrict__ off,
+                                          int* __restrict__ frozen, int* __restrict__ sweeps_done, int batch, int sweeps) {
+    for (int b = threadIdx.x; b < batch; b += blockDim.x) {
+        if (frozen[b]) continue;
+        sweeps_done[b] += sweeps;
+        if (off[b] <= tol[b]) frozen[b] = 1;
+    }
 }
 
 // Whole decomposition of a SMALL matrix (n <= 128 columns) in ONE launch: one workgroup per matrix of the
@@ -812,6 +852,23 @@ void launch_jacobi_round(double* W, long long ldw, double* V, long long ldv, int
         hipLaunchKernelGGL(jacobi_round_kernel<0>, dim3(ne / 2), dim3(256), 0, st, W, ldw, V, ldv, m, n, ne, r, off);
 }
 
+// The shapes the block kernel takes (without V), the shapes a ragged batch takes (those, up to JB_MAXM columns) and the
+// kernel's LDS limit.
+bool jacobi_block_shape(int m, int n) { return m >= 1 && m <= JB_MAXM && n > 4 * JB; }
+bool jacobi_batch_shape(int m, int n) { return jacobi_block_shape(m, n) && n <= JB_MAXM; }
+bool jacobi_block_raise_lds() {
+    static bool attr_set = false;
+    if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_block_kernel<true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * JB * JB_MAXM * (int)sizeof(double)) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_block_kernel<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * JB * JB_MAXM * (int)sizeof(double)) != hipSuccess)
+            return false;
+        attr_set = true;
+    }
+    return true;
+}
+
 // 0 = not supported, else the V mode the small kernel would use
 int jacobi_small_vmode(int m, int n, int want_v) {
     if (m < 1 || n < 1 || n > JS_MAX_N || m > JS_MAX_N) return -1;
@@ -970,21 +1027,12 @@ extern "C" int xps_jacobi_sweeps_f64(double* W, int64_t ldw, double* V, int64_t 
         if (off && hipMemsetAsync(off, 0, sizeof(double), st) != hipSuccess) return XPS_E_HIP;
         return XPS_OK;
     }
-    const bool block_path = (V == nullptr) && m <= JB_MAXM && n > 4 * JB;
-    const int nb = ((n + JB - 1) / JB + 1) & ~1;         // blocks, padded to an even count
+    const bool block_path = jacobi_block_shape(m, n) && V == nullptr;
+    const int nb = jacobi_block_count(n);                // blocks, padded to an even count
     const size_t block_lds = (size_t)2 * JB * m * sizeof(double);
-    if (block_path) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_block_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * JB * JB_MAXM * (int)sizeof(double)) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_block_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * JB * JB_MAXM * (int)sizeof(double)) != hipSuccess) {
-                xps_set_error("xps_jacobi_sweeps_f64: cannot raise the dynamic LDS limit");
-                return XPS_E_HIP;
-            }
-            attr_set = true;
-        }
+    if (block_path && !jacobi_block_raise_lds()) {
+        xps_set_error("xps_jacobi_sweeps_f64: cannot raise the dynamic LDS limit");
+        return XPS_E_HIP;
     }
     for (int s = 0; s < sweeps; ++s) {
         const bool last = (s == sweeps - 1);
@@ -997,10 +1045,10 @@ extern "C" int xps_jacobi_sweeps_f64(double* W, int64_t ldw, double* V, int64_t 
         if (block_path) {
             unsigned long long* ob = (last && off) ? (unsigned long long*)off : nullptr;
             hipLaunchKernelGGL(jacobi_block_kernel<false>, dim3(nb / 2), dim3(512), block_lds, st, W, (long long)ldw, m, n, nb,
-                               0, ob);
+                               0, ob, JacobiBatch{});
             for (int r = 0; r < nb - 1; ++r)
                 hipLaunchKernelGGL(jacobi_block_kernel<true>, dim3(nb / 2), dim3(512), block_lds, st, W, (long long)ldw, m, n,
-                                   nb, r, ob);
+                                   nb, r, ob, JacobiBatch{});
             XPS_CHECK_LAUNCH();
             continue;
         }
@@ -1010,5 +1058,66 @@ extern "C" int xps_jacobi_sweeps_f64(double* W, int64_t ldw, double* V, int64_t 
         }
         XPS_CHECK_LAUNCH();
     }
+    return XPS_OK;
+}
+
+extern "C" int xps_jacobi_batched_supported(int m, int n) { return jacobi_batch_shape(m, n); }
+
+extern "C" size_t xps_jacobi_sweeps_batched_f64_workspace(int batch) {
+    return batch < 0 ? 0 : ((size_t)batch + 1) * (2 * sizeof(long long) + 2 * sizeof(int));
+}
+
+extern "C" int xps_jacobi_sweeps_batched_f64(double* W, int64_t w_len, const int64_t* w_off, const int64_t* ldw, const int* m,
+                                             const int* n, int batch, int sweeps, int check, const double* tol, double* off,
+                                             int32_t* frozen, int32_t* sweeps_done, void* ws, size_t ws_bytes, void* stream) {
+    XPS_CHECK_ARG(W && w_off && ldw && m && n && tol && off && frozen && sweeps_done && ws, "null argument");
+    XPS_CHECK_ARG(batch >= 0 && batch <= 65535 && sweeps >= 0 && w_len >= 0, "bad parameter");
+    XPS_CHECK_ARG(ws_bytes >= xps_jacobi_sweeps_batched_f64_workspace(batch), "workspace too small");
+    int max_nb = 0, max_m = 0;
+    for (int b = 0; b < batch; ++b) {                                // w_off / ldw / m / n are HOST arrays: checked here, then copied
+        if (!jacobi_batch_shape(m[b], n[b])) {
+            xps_set_error("xps_jacobi_sweeps_batched_f64: matrix %d is %d x %d: not a shape of the block kernel", b, m[b], n[b]);
+            return XPS_E_INVALID;
+        }
+        XPS_CHECK_ARG(ldw[b] >= m[b], "leading dimension too small (column-major)");
+        XPS_CHECK_ARG(w_off[b] >= 0 && w_off[b] <= w_len && m[b] <= w_len - w_off[b] &&
+                      n[b] - 1 <= (w_len - w_off[b] - m[b]) / ldw[b], "a matrix reaches outside the buffer");
+        const int nb = jacobi_block_count(n[b]);
+        max_nb = nb > max_nb ? nb : max_nb;
+        max_m = m[b] > max_m ? m[b] : max_m;
+    }
+    if (batch == 0) return XPS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (!jacobi_block_raise_lds()) {
+        xps_set_error("xps_jacobi_sweeps_batched_f64: cannot raise the dynamic LDS limit");
+        return XPS_E_HIP;
+    }
+    static_assert(sizeof(long long) == sizeof(int64_t), "w_off / ldw are read as long long");
+    long long* off_d = static_cast<long long*>(ws);
+    long long* ldw_d = off_d + batch;
+    int* m_d = reinterpret_cast<int*>(ldw_d + batch);
+    int* n_d = m_d + batch;
+    hipError_t e = hipMemcpyAsync(off_d, w_off, (size_t)batch * sizeof(long long), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(ldw_d, ldw, (size_t)batch * sizeof(long long), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(m_d, m, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(n_d, n, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { xps_set_error("%s: copying the tables failed: %s", __func__, hipGetErrorString(e)); return XPS_E_HIP; }
+    const JacobiBatch tab{off_d, ldw_d, m_d, n_d, (const int*)frozen};
+    const size_t block_lds = (size_t)2 * JB * max_m * sizeof(double);
+    const dim3 grid(max_nb / 2, batch);
+    if (sweeps == 0) hipLaunchKernelGGL(jacobi_batch_begin_kernel, dim3(cdiv(batch, 256)), dim3(256), 0, st, off, tab.frozen, batch);
+    for (int s = 0; s < sweeps; ++s) {
+        const bool last = (s == sweeps - 1);
+        if (last) hipLaunchKernelGGL(jacobi_batch_begin_kernel, dim3(cdiv(batch, 256)), dim3(256), 0, st, off, tab.frozen, batch);
+        unsigned long long* ob = last ? (unsigned long long*)off : nullptr;
+        hipLaunchKernelGGL(jacobi_block_kernel<false>, grid, dim3(512), block_lds, st, W, 0LL, 0, 0, 0, 0, ob, tab);
+        for (int r = 0; r < max_nb - 1; ++r)
+            hipLaunchKernelGGL(jacobi_block_kernel<true>, grid, dim3(512), block_lds, st, W, 0LL, 0, 0, 0, r, ob, tab);
+        XPS_CHECK_LAUNCH();
+    }
+    if (check && sweeps > 0)
+        hipLaunchKernelGGL(jacobi_batch_check_kernel, dim3(1), dim3(256), 0, st, tol, (const double*)off, (int*)frozen,
+                           (int*)sweeps_done, batch, sweeps);
+    XPS_CHECK_LAUNCH();
     return XPS_OK;
 }

@@ -10,7 +10,7 @@ passes (CPU, as in the reference)."""
 import numpy as np
 from sklearn.base import BaseEstimator
 
-from ..alignment.pca import PCA
+from ..alignment.pca import PCA, fit_many
 
 
 def _flat(x):
@@ -47,6 +47,14 @@ class crossPtDecoder(BaseEstimator):
         """Independent reduction of the target and of every pooled patient over (trial*time, channel) rows.
         Returns the target (3-D), the pooled patients (3-D) and keeps the target model for the test set."""
         out = []
+        if self.dim_red is PCA:
+            # covariance-side PCAs: one eigendecomposition call for all patients (same fitted models, bit for bit)
+            xs = [x for x, _, _ in self.cross_pt_data] + [X]
+            models = fit_many([x.reshape(-1, x.shape[-1]) for x in xs], n_components=self.n_comp)
+            zs = [m.transform(x.reshape(-1, x.shape[-1])) for m, x in zip(models, xs)]
+            self.tar_dr = models[-1]
+            out = [z.reshape(x.shape[0], -1, z.shape[-1]) for z, x in zip(zs[:-1], xs)]
+            return zs[-1].reshape(X.shape[0], -1, zs[-1].shape[-1]), out
         for x, _, _ in self.cross_pt_data:
             z = self.dim_red(n_components=self.n_comp).fit_transform(x.reshape(-1, x.shape[-1]))
             out.append(z.reshape(x.shape[0], -1, z.shape[-1]))

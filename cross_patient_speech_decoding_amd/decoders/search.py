@@ -243,7 +243,8 @@ def build_plan(estimator, split_candidates, X, yi, classes, splits, plan=None, o
 
 def build_plan_pca(estimator, split_candidates, X, yi, classes, splits):
     """The plan of a ``batch_pca=True`` search.  Device: one upload of X, the column mean, one Gram product, one centring launch
-    for all folds, the Jacobi launches (one per distinct training size) and one grouped apply for the scores Z_f of every fold.
+    for all folds, ONE eigh_psd_batched call (one launch per distinct training size the one-workgroup Jacobi takes, one ragged
+    batch for the larger ones) and one grouped apply for the scores Z_f of every fold.
     Host: per (fold, n_components) the cut r and whether it is batched (``pca_cut``), gamma from the spectrum (``pca_gamma``).  A
     batched (fold, r, gamma) is a kernel matrix whose view is ``('pca', fold, r)``; the other (candidate, fold) pairs go through
     ``build_plan``'s views inside the same plan.  ``split_candidates``: ``split_params_pca`` of every candidate."""
@@ -261,11 +262,7 @@ def build_plan_pca(estimator, split_candidates, X, yi, classes, splits):
     n_tr = [len(tr) for tr, _ in splits]
     n_all = [len(tr) + len(te) for tr, te in splits]
     blocks = [Kc_h[offs[f]:offs[f + 1]].reshape(n_all[f], n_tr[f])[:n_tr[f]] for f in range(nf)]
-    eig = [None] * nf
-    for size in sorted(set(n_tr)):                              # stacked by size: folds differ in size by one
-        fs = [f for f in range(nf) if n_tr[f] == size]
-        for f, res in zip(fs, LA.eigh_psd_batched(np.stack([0.5 * (blocks[f] + blocks[f].T) for f in fs]))):
-            eig[f] = res
+    eig = LA.eigh_psd_batched([0.5 * (blocks[f] + blocks[f].T) for f in range(nf)])     # folds differ in size by one: one call
     plan = Plan()
     ncs = [b.get('n_components', red.n_components) for b, _ in split_candidates]
     comps = np.zeros((len(ncs), nf), dtype=np.int64)

@@ -608,6 +608,24 @@ int xps_prefix_kernels_f64(const int64_t* problems, int n_problems, const int32_
 size_t xps_jacobi_f64_workspace(int n);
 int xps_jacobi_sweeps_f64(double* W, int64_t ldw, double* V, int64_t ldv, int m, int n, int sweeps,
                           double* off, void* workspace, size_t workspace_bytes, void* stream);
+/* A ragged batch through the block kernel of xps_jacobi_sweeps_f64: `batch` column-major matrices of different (m, n, ldw)
+ * in ONE device buffer W of w_len doubles, matrix b at W + w_off[b] (the matrices must not overlap: not checked).
+ * xps_jacobi_batched_supported(m, n): the shapes the block kernel takes (no V, m <= 1024, n > 32) up to 1024 columns;
+ * anything else is refused.  `sweeps` sweeps run on every matrix with frozen[b] == 0: one launch per block round covers
+ * the batch (1 + max_nb - 1 launches a sweep, max_nb over the batch), and a matrix's iterates are those of
+ * xps_jacobi_sweeps_f64 on it alone, bit for bit.  off[b] (DEVICE) receives the largest |cos angle| of the call's last
+ * sweep; frozen matrices keep theirs.  check != 0: after the last sweep, on the device, the matrices that ran add `sweeps`
+ * to sweeps_done[b] and set frozen[b] = 1 where off[b] <= tol[b].  tol, off, frozen and sweeps_done are DEVICE arrays of
+ * `batch` elements that the caller owns and initialises.  w_off, ldw, m and n are HOST arrays: the call checks them (every
+ * matrix inside W, ldw >= m, a supported shape: XPS_E_INVALID before any HIP call) and copies them into ws (DEVICE,
+ * xps_jacobi_sweeps_batched_f64_workspace(batch) bytes) on the stream; they must stay valid until the stream has passed
+ * the call.  batch > 65535 (the grid's second dimension) is refused too.  Nothing synchronises.  batch == 0: XPS_OK,
+ * nothing is launched. */
+int xps_jacobi_batched_supported(int m, int n);
+size_t xps_jacobi_sweeps_batched_f64_workspace(int batch);
+int xps_jacobi_sweeps_batched_f64(double* W, int64_t w_len, const int64_t* w_off, const int64_t* ldw, const int* m,
+                                  const int* n, int batch, int sweeps, int check, const double* tol, double* off,
+                                  int32_t* frozen, int32_t* sweeps_done, void* ws, size_t ws_bytes, void* stream);
 /* Small problems (n <= 128 columns, n*m doubles within one workgroup's LDS): the WHOLE decomposition of each of
  * `batch` matrices (stride_w / stride_v doubles apart) in one launch, one workgroup per matrix; sweeps run
  * until the largest |cos angle| of a sweep is <= tol or max_sweeps.  V (optional) is SET to the accumulated
