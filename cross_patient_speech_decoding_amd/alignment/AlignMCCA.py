@@ -14,10 +14,10 @@ implements the published regularised SUMCOR-MCCA generalised eigenproblem on the
   loadings = rows of S V_k per view; sign rule on the normalised common scores
   transform_view(X, i) = (X - mean_i) @ loadings_i                        xps_apply_f64
 """
-import os
 
 import numpy as np
 
+from .. import _switches
 from . import _linalg as LA
 from .alignment_utils import _group_conditions_device
 from .pca import sign_rule
@@ -150,7 +150,7 @@ def _gevp(Gd, offs, n_components, regs):
     D = Gd.shape[0]
     LHS = Gd.clone()
     S = None
-    if regs and os.environ.get('XPS_MCCA_WHITEN', 'chol') != 'eig':
+    if regs and _switches.get('XPS_MCCA_WHITEN') != 'eig':
         # regularised blocks R_b = (1 - r) G_bb + r I are positive definite with condition <= (lambda_max + r) / r: whitened by
         # their Cholesky factors, S = blockdiag(L_b^-T), in ONE launch (the symmetric R_b^-1/2 from eight 128 x 128 Jacobi
         # eigendecompositions was 5 of the 17.5 ms of this function; the eigenvectors S u of the pencil are the same)

@@ -5,11 +5,11 @@ f64 MFMA, Jacobi eigen/singular decompositions, batched transform apply — runs
 Host numpy only sorts / normalises / sign-fixes the small (d x d) results and builds index
 lists; there is no CPU fallback for the kernels.
 """
-import os
 
 import numpy as np
 import torch
 
+from .. import _switches
 from .._dev import current_device, ptr, stream, workspace
 from .._lib import call, lib
 
@@ -570,7 +570,7 @@ def _orthonormal_columns(Y):
     """Orthonormal basis of the column span of Y (n x m device matrix, m << n).  Shifted Cholesky QR (above) where it
     succeeds; else -- and always with XPS_TOPK_ORTHO=jacobi -- one-sided Jacobi on Y itself (no Gram matrix: a filtered block
     whose columns differ in size by 1e7 keeps its small directions).  None if rank was lost."""
-    if os.environ.get('XPS_TOPK_ORTHO', 'chol') != 'jacobi':
+    if _switches.get('XPS_TOPK_ORTHO') != 'jacobi':
         Q = _orthonormal_columns_cholqr3(Y)
         if Q is not None:
             return Q

@@ -18,28 +18,22 @@
 // time-major outputs.
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 #include "xps_common.h"
 #include "xps_gemm_tile.h"
 #include "xps_gemm_big.h"
 #include "xps_gemm_dma.h"
+#include "xps_switches.h"
 using namespace xps_tile;
-#ifndef XPS_GEMM_DEFAULT_MODE
-#define XPS_GEMM_DEFAULT_MODE 1
-#endif
 namespace {
 
 // C (+)= A B (+ A2 B2) + bias.  MI = 1: 64 x 128 tiles (twice the blocks, for grids that would not fill
 // the chip with 128 x 128 tiles);  A2/B2: an optional second operand pair with the same row maps (the two
 // directions of a bidirectional layer summed in registers instead of a second accumulate pass).
 // 64-row tiles of the bf16 pipeline use 36 KB of LDS per block, so four blocks would fit a CU if the kernel kept to 128
-// registers (-DXPS_BF_MI1_WAVES=4).  Measured: the projections gain 3-6 %, the two-operand input-gradient form loses 15 %
+// registers (__launch_bounds__(256, 4)).  Measured: the projections gain 3-6 %, the two-operand input-gradient form loses 15 %
 // to spills, the step is unchanged — three blocks per CU stay the default.
-#ifndef XPS_BF_MI1_WAVES
-#define XPS_BF_MI1_WAVES XPS_GEMM_WAVES
-#endif
 template <bool AK, bool BK, int MI, bool EDGE = false, bool BF = false, bool PRE = false>      // PRE: XPS_FMT_SPLIT4 operands (bf16x3 only)
-__global__ __launch_bounds__(256, (BF && MI == 1) ? XPS_BF_MI1_WAVES : XPS_GEMM_WAVES) void gemm_f32_kernel(
+__global__ __launch_bounds__(256, GEMM_WAVES) void gemm_f32_kernel(
     const float* __restrict__ A, RowMap ra, const float* __restrict__ B, RowMap rb,
     const float* __restrict__ A2, const float* __restrict__ B2, int K2,
     float* __restrict__ C, RowMap rc, const float* __restrict__ bias,
@@ -145,7 +139,7 @@ struct NtMulti {
     float* C[4];
 };
 template <int MI, bool EDGE = false, bool BF = false, bool PRE = false>
-__global__ __launch_bounds__(256, (BF && MI == 1) ? XPS_BF_MI1_WAVES : XPS_GEMM_WAVES) void gemm_nt_multi_kernel(
+__global__ __launch_bounds__(256, GEMM_WAVES) void gemm_nt_multi_kernel(
     const float* __restrict__ A, RowMap ra, NtMulti pm, RowMap rb, RowMap rc, int M, int N, int K, int nprob,
     int vecA, int vecB) {
     __shared__ __attribute__((aligned(16))) TileMem<BF, MI> mem;
@@ -187,16 +181,14 @@ __global__ __launch_bounds__(256, (BF && MI == 1) ? XPS_BF_MI1_WAVES : XPS_GEMM_
 // consecutive columns of one row; 8 store instructions instead of 32; same bits) were built and measured -- every instruction
 // then touches 32 rows x 32 bytes, and the launches take 125-130 / 112-117 / 56 us instead of 85-92 / 43-45 / 28 us on the three
 // shapes above (configs[3] step + 0.3 ms): full lines per instruction matter more than the instruction count.  Not kept.
+constexpr int WS_PAD = 4;
 template <int KT>
 __global__ __launch_bounds__(512, 1) void proj_ws_kernel(const float* __restrict__ A, long long lda, NtMulti pm, long long ldb, long long ldc,
                                                          int M, int N, int K, int nprob, int preA, int preB) {
     constexpr int KP = 16 * KT;                       // padded k extent (multiple of 32)
-#ifndef XPS_WS_PAD
-#define XPS_WS_PAD 4
-#endif
     // LDS row stride in dwords (2 bf16 each), = 4 (mod 64): the b128 fragment reads (32 rows x one k-half per half-wave; lane
     // groups {0-3,12-15,20-27}, ...: MI355X_MICROARCH.md, LDS) then touch 16 distinct 4-bank groups per cycle
-    constexpr int LDH = ((KP / 2 + 63) / 64) * 64 + XPS_WS_PAD;
+    constexpr int LDH = ((KP / 2 + 63) / 64) * 64 + WS_PAD;
     constexpr int NV = KP / 32;                       // 16-byte vectors per thread and tile (64 rows x KP / 4 vectors / 512 threads)
     extern __shared__ __attribute__((aligned(16))) unsigned char ws_smem[];
     unsigned* lds = reinterpret_cast<unsigned*>(ws_smem);          // [buffer 2][plane hi, lo][64 rows][LDH dwords]
@@ -291,7 +283,7 @@ __global__ __launch_bounds__(512, 1) void proj_ws_kernel(const float* __restrict
         }
     }
 }
-constexpr int proj_ws_lds(int KT) { return 2 * 2 * 64 * (((16 * KT / 2 + 63) / 64) * 64 + XPS_WS_PAD) * 4; }
+constexpr int proj_ws_lds(int KT) { return 2 * 2 * 64 * (((16 * KT / 2 + 63) / 64) * 64 + WS_PAD) * 4; }
 
 // Grouped TN GEMM: up to TN_MAXP weight-gradient problems  C_p = A_p^T B_p  (+ column sums of A_p
 // from the LDS copy of the A tiles = the bias gradient) in ONE launch; every block owns one
@@ -347,7 +339,7 @@ __device__ inline void slab_decode(int e, int& row, int& col) {
 }
 
 template <bool EDGE, bool BF = false, bool PRE = false>
-__global__ __launch_bounds__(256, XPS_GEMM_WAVES) void gemm_tn_grouped_kernel(TnGroup g, float* __restrict__ ws) {
+__global__ __launch_bounds__(256, GEMM_WAVES) void gemm_tn_grouped_kernel(TnGroup g, float* __restrict__ ws) {
     __shared__ __attribute__((aligned(16))) TileMem<BF> mem;
     // Logical order, uniform groups (the weight gradients of a GRU layer: same K = T' x B rows for every problem):
     // (k-split, problem, tile) -- ALL blocks that read rows [kbeg, kend) of the operands are neighbours on one XCD and run at
@@ -752,43 +744,26 @@ namespace {
 // Product precision of the tile kernels: 0 = fp32 MFMA (exact fp32 fma chains), 1 = bf16 split products (3 bf16 MFMAs
 // per product, ~2^-16 relative product error, fp32 accumulate).  Process-wide; XPS_GEMM_PRECISION=fp32|bf16x3 sets the
 // initial value, xps_set_gemm_precision() changes it (not while launches of another thread are in flight).
-std::atomic<int>& gemm_mode() {
-    static std::atomic<int> mode([] {
-        const char* e = getenv("XPS_GEMM_PRECISION");
-        if (e && (!strcmp(e, "fp32") || !strcmp(e, "f32") || !strcmp(e, "0"))) return 0;
-        if (e && (!strcmp(e, "bf16x3") || !strcmp(e, "1"))) return 1;
-        return XPS_GEMM_DEFAULT_MODE;
-    }());
-    return mode;
-}
-inline bool bf_mode() { return gemm_mode().load(std::memory_order_relaxed) == 1; }
+inline bool bf_mode() { return xps_sw::get(xps_sw::GEMM_PRECISION) == 1; }
 
 // 64-row tiles when 128-row tiles would leave the chip under-filled (< ~2 blocks per CU)
 // (long contractions -- the rows a 256-tile launch leaves behind, K >= 1024 -- are issue-bound, not HBM-bound: there the 128-row
 //  tile's better MFMA-per-staged-element ratio wins as soon as every CU gets two blocks)
 inline bool use_small_tiles(int M, int N, int K = 0) {
-    static const int thr = [] {
-        const char* e = getenv("XPS_GEMM_SMALL_TILE_BLOCKS");
-        int v = e ? atoi(e) : -1;
-        return v >= 0 ? v : 2048;
-    }();
+    const long long thr = xps_sw::get(xps_sw::GEMM_SMALL_TILE_BLOCKS);
     const long long n128 = (long long)cdiv(M, 128) * cdiv(N, BN);
-    static const bool longk = [] { const char* e = getenv("XPS_GEMM_LONGK_128"); return !(e && e[0] == '0'); }();
+    const bool longk = xps_sw::on(xps_sw::GEMM_LONGK_128);
     if (longk && K >= 1024 && n128 >= 512) return false;
     return M > 64 && n128 < thr;
 }
 
 // 256 x 256 tiles (xps_gemm_big.h): bf16 split-product mode, whole tiles only, plain 16-byte aligned operands, and
 // enough tiles to give every CU one.  XPS_GEMM_BIG=0 switches the path off (A/B runs, tests of the small-tile kernels).
-std::atomic<int>& big_switch() {
-    static std::atomic<int> on([] { const char* e = getenv("XPS_GEMM_BIG"); return (e && e[0] == '0') ? 0 : 1; }());
-    return on;
-}
-inline bool big_enabled() { return big_switch().load(std::memory_order_relaxed) != 0 && bf_mode(); }
-// LDS-DMA k loop of the 256-tile weight-gradient kernel (xps_gemm_dma.h); XPS_GEMM_DMA=0 (read per call: A/B tests toggle it)
-inline bool dma_enabled() { const char* e = getenv("XPS_GEMM_DMA"); return !(e && e[0] == '0'); }
-// weight-stationary projection kernel (proj_ws_kernel): XPS_PROJ_WS=0 keeps the tile kernels (read per call: A/B tests toggle it)
-inline bool proj_ws_enabled() { const char* e = getenv("XPS_PROJ_WS"); return !(e && e[0] == '0'); }
+inline bool big_enabled() { return xps_sw::on(xps_sw::GEMM_BIG) && bf_mode(); }
+// LDS-DMA k loop of the 256-tile weight-gradient kernel (xps_gemm_dma.h); XPS_GEMM_DMA=0 keeps the register-staged loop
+inline bool dma_enabled() { return xps_sw::on(xps_sw::GEMM_DMA); }
+// weight-stationary projection kernel (proj_ws_kernel): XPS_PROJ_WS=0 keeps the tile kernels
+inline bool proj_ws_enabled() { return xps_sw::on(xps_sw::PROJ_WS); }
 inline bool big_plain(const float* p, const RowMap& r, int rows) { return aligned16(p) && r.ld % 4 == 0 && r.rpg >= rows; }
 constexpr int BIG_LDS = (int)sizeof(xps_big::BigStage), BIG_LDS32 = (int)sizeof(xps_big::BigStage32);
 constexpr int BIG_TN_LDS = BIG_LDS > xps_big::DMA_LDS ? BIG_LDS : xps_big::DMA_LDS;      // the weight-gradient kernel holds both k loops
@@ -800,14 +775,8 @@ inline bool big_prepare(Kern kern, int bytes) {
 // 32-deep stages (opt-in: XPS_GEMM_BIG_DEEP=1, and only where every k range is a multiple of 32).  Measured: the single
 // launches gain (projection 418 -> 396 us, input gradient 423 -> 392 us, 8192^3 0.40 -> 0.45 of peak; the TN form loses
 // 1-5 %), the configs[3] step does not (8.26-8.27 vs 8.20-8.23 ms, A/B on one box): 16-deep stays the default.
-inline bool big_deep_allowed() {
-    static const bool on = [] { const char* e = getenv("XPS_GEMM_BIG_DEEP"); return e && e[0] == '1'; }();
-    return on;
-}
-inline int big_min_tiles() {
-    static const int v = [] { const char* e = getenv("XPS_GEMM_BIG_MIN_TILES"); int x = e ? atoi(e) : 0; return x > 0 ? x : 192; }();
-    return v;
-}
+inline bool big_deep_allowed() { return xps_sw::on(xps_sw::GEMM_BIG_DEEP); }
+inline long long big_min_tiles() { return xps_sw::get(xps_sw::GEMM_BIG_MIN_TILES); }
 
 inline int device_cus() {
     static const int cus = [] {
@@ -823,7 +792,7 @@ inline int device_cus() {
 // round) -- same bits either way (both tile shapes accumulate a product whose k range is not split in the same order).
 // Returns the number of leading ROWS for the 256-tile launch (== M: no split).  XPS_GEMM_BIG_TAIL=0: never split.
 inline int big_split_rows(int M, int tiles_per_row_tile) {
-    static const bool on = [] { const char* e = getenv("XPS_GEMM_BIG_TAIL"); return !(e && e[0] == '0'); }();
+    const bool on = xps_sw::on(xps_sw::GEMM_BIG_TAIL);
     const int cus = device_cus();
     const long long mt = M / xps_big::TM, total = mt * tiles_per_row_tile;
     const long long rounds = total / cus, rem = total % cus;
@@ -1160,11 +1129,8 @@ extern "C" int xps_gemm_tn_f32(const float* A, const xps_rowmap* ra_, const floa
 namespace {
 int build_group(const xps_tn_problem* probs, int n, TnGroup& g, size_t& ws_floats, int big_choice = -1) {
     if (n < 1 || n > TN_MAXP) return -1;
-    static const int target_blocks = [] {
-        const char* e = getenv("XPS_TN_BLOCKS");
-        int v = e ? atoi(e) : 0;
-        return v > 0 ? v : 512;              // (768 until the flat reduce existed: 512 + flat is -5 % on the cfg-2 step, -1.7 % on configs[3])
-    }();
+    // (default 512; 768 until the flat reduce existed: 512 + flat is -5 % on the cfg-2 step, -1.7 % on configs[3])
+    const int target_blocks = (int)xps_sw::get(xps_sw::TN_BLOCKS);
     // problems the 256 x 256 kernel takes (whole tiles, plain aligned operands, a long k range); the others stay on
     // the 128 x 128 kernel.  Each class shares its own block budget among its problems in proportion to their tiles.
     const bool big_on = big_choice < 0 ? big_enabled() : big_choice != 0;      // (workspace query: both tilings)
@@ -1242,7 +1208,7 @@ int build_group(const xps_tn_problem* probs, int n, TnGroup& g, size_t& ws_float
     for (int i = 1; i < n; ++i) same_k = same_k && probs[i].K == probs[0].K;
     // opt-in (XPS_TN_UNIFORM=1): measured twice (rounds 1 and 2, cfg-2 layer-1 group) -- same launch time (151 vs 152 us) and
     // the same fabric traffic within 1 %: co-resident blocks drift apart by more k-tiles than an XCD's L2 holds
-    static const bool allow = [] { const char* e = getenv("XPS_TN_UNIFORM"); return e && e[0] == '1'; }();
+    const bool allow = xps_sw::on(xps_sw::TN_UNIFORM);
     if (same_k && allow && probs[0].K > 0 && blocks_big == 0) {
         int sp = (int)((target_blocks + tiles_total - 1) / tiles_total);
         const int maxs = cdiv(probs[0].K, 64);
@@ -1308,8 +1274,7 @@ extern "C" int xps_gemm_tn_grouped_f32(const xps_tn_problem* probs, int n, void*
         }
         // measured: the [k][x] x [k][x] form gains nothing from 32-deep stages (its fetches are full lines already) and loses
         // 1-5 % to the larger LDS block: 16-deep unless XPS_GEMM_BIG_DEEP_TN=1
-        static const bool deep_tn = [] { const char* e = getenv("XPS_GEMM_BIG_DEEP_TN"); return e && e[0] == '1'; }();
-        bool deep = big_deep_allowed() && deep_tn;
+        bool deep = big_deep_allowed() && xps_sw::on(xps_sw::GEMM_BIG_DEEP_TN);
         for (int i = 0; i < n; ++i) deep = deep && (!g.p[i].big || (g.p[i].kchunk % 32 == 0 && g.p[i].K % 32 == 0 && !((g.p[i].vecA | g.p[i].vecB) & 2)));
         if (deep)
             hipLaunchKernelGGL(gemm_big_tn_kernel<true>, dim3(g.total_blocks_big), dim3(xps_big::NTHR), BIG_LDS32, (hipStream_t)stream, g,
@@ -1335,7 +1300,7 @@ extern "C" int xps_gemm_tn_grouped_f32(const xps_tn_problem* probs, int n, void*
     XPS_CHECK_LAUNCH();
     int max_splits = 1;
     for (int i = 0; i < n; ++i) max_splits = g.p[i].splits > max_splits ? g.p[i].splits : max_splits;
-    static const int red_mode = [] { const char* e = getenv("XPS_TN_REDUCE"); return !e ? 0 : (e[0] == 'f' ? 1 : (e[0] == 'l' ? 2 : 0)); }();
+    const long long red_mode = xps_sw::get(xps_sw::TN_REDUCE);
     if (red_mode == 1 || (red_mode == 0 && max_splits <= 32))
         hipLaunchKernelGGL(gemm_tn_grouped_reduce_flat, dim3(cdiv(g.total_out, 256 * 4)), dim3(256), 0, (hipStream_t)stream, g,
                            (const float*)workspace);
@@ -1346,23 +1311,23 @@ extern "C" int xps_gemm_tn_grouped_f32(const xps_tn_problem* probs, int n, void*
     return XPS_OK;
 }
 
-int xps_internal_gemm_mode() { return gemm_mode().load(std::memory_order_relaxed); }
+int xps_internal_gemm_mode() { return (int)xps_sw::get(xps_sw::GEMM_PRECISION); }
 
 extern "C" int xps_set_gemm_precision(int mode) {
     XPS_CHECK_ARG(mode == 0 || mode == 1, "mode: 0 = fp32 MFMA, 1 = bf16 split products");
-    gemm_mode().store(mode);
+    xps_sw::store(xps_sw::GEMM_PRECISION, mode);
     return XPS_OK;
 }
 
-extern "C" int xps_get_gemm_precision(void) { return gemm_mode().load(); }
+extern "C" int xps_get_gemm_precision(void) { return xps_internal_gemm_mode(); }
 
 extern "C" int xps_set_gemm_big_tiles(int on) {
     XPS_CHECK_ARG(on == 0 || on == 1, "on: 0 = 128 x 128 tiles only, 1 = 256 x 256 tiles for large interior shapes");
-    big_switch().store(on);
+    xps_sw::store(xps_sw::GEMM_BIG, on);
     return XPS_OK;
 }
 
-extern "C" int xps_get_gemm_big_tiles(void) { return big_switch().load(); }
+extern "C" int xps_get_gemm_big_tiles(void) { return (int)xps_sw::get(xps_sw::GEMM_BIG); }
 
 #ifdef XPS_GSTAMP
 extern "C" int xps_debug_read_gstamps(unsigned long long* host, int n) {

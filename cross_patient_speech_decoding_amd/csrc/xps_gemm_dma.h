@@ -24,20 +24,14 @@
 
 namespace xps_big {
 
-#ifndef XPS_DMA_STAGES
-#define XPS_DMA_STAGES 4
-#endif
-constexpr int DMA_D = XPS_DMA_STAGES;
+constexpr int DMA_D = 4;
 constexpr int DMA_ROW = 1024;
 constexpr int DMA_QPAD = 144;
 constexpr int DMA_IMG = 16 * DMA_ROW + 4 * DMA_QPAD;          // 16960 B: one operand, one k-tile
 constexpr int DMA_STAGE = 2 * DMA_IMG;                        // A then B
 constexpr int DMA_LDS = DMA_D * DMA_STAGE;                    // 135680 B
-#ifndef XPS_DMA_SHIFT8
-#define XPS_DMA_SHIFT8 1
-#endif
 __host__ __device__ constexpr int dma_rowoff(int k) {
-    return k * DMA_ROW + (k >> 2) * DMA_QPAD + ((k & 1) ? (XPS_DMA_SHIFT8 ? 8 : 0) : 0) + ((k & 2) ? 128 : 0);
+    return k * DMA_ROW + (k >> 2) * DMA_QPAD + ((k & 1) ? 8 : 0) + ((k & 2) ? 128 : 0);
 }
 constexpr int DMA_ROW4 = 4 * DMA_ROW + DMA_QPAD;              // rowoff(k + 4) - rowoff(k)
 
@@ -60,20 +54,6 @@ __device__ inline void dma_piece(const unsigned char* sbase, unsigned voff, unsi
                  : "v"(voff), "s"(sbase), "s"(ldst)
                  : "memory");
 }
-
-#ifndef XPS_DMA_SPREAD
-#define XPS_DMA_SPREAD 1
-#endif
-#ifndef XPS_DMA_STAGGER
-#define XPS_DMA_STAGGER 0
-#endif
-// XPS_DMA_PAIR=1: two k-tiles per barrier (below).  Measured level with one barrier per k-tile (tools/proto/tn_dma.hip, dW_ih of
-// configs[3], two interleaved runs each: 318.7 / 321.5 us against 319.5 / 321.5 us, same bits) -- like the staggered and the
-// merged-barrier forms before it: with 65 % of the cycles on the matrix pipe at the 1.77 GHz the power limit leaves, removing
-// idle cycles does not buy time.  Compiled out.
-#ifndef XPS_DMA_PAIR
-#define XPS_DMA_PAIR 0
-#endif
 
 // acc += A[kbeg .. kbeg + 16 nkt)^T B[...] for the 256 x 256 tile at (m0, n0); A, B: split4 operands, [k][x], leading
 // dimensions lda / ldb (elements).  Ends with every DMA piece landed and a barrier (LDS is free).
@@ -129,7 +109,7 @@ __device__ inline void tn_dma_pipeline(f32x16 (&acc)[4][2], f32x16& cacc, const 
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.0f;
 #pragma unroll
-    for (int d = 0; d < (XPS_DMA_PAIR && DMA_D == 4 && !XPS_DMA_STAGGER ? 2 : DMA_D - 1); ++d)
+    for (int d = 0; d < DMA_D - 1; ++d)
 #pragma unroll
         for (int pc = 0; pc < 4; ++pc) piece(d, pc);
 #ifdef XPS_DMA_STAMP
@@ -162,134 +142,13 @@ __device__ inline void tn_dma_pipeline(f32x16 (&acc)[4][2], f32x16& cacc, const 
             }
         }
     };
-    auto wait_tile = [&]() {
-        if constexpr (DMA_D == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // this wave's pieces of k-tile kt have landed
-        else if constexpr (DMA_D == 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    if (XPS_DMA_STAGGER && wave >= 4) {
-        // Waves 4-7 (the SIMD partners of waves 0-3) run HALF A K-TILE BEHIND: the MFMAs of row groups 2, 3 of a k-tile are issued
-        // after the NEXT barrier, from fragments read before it (every LDS read of a stage still precedes the barrier that frees
-        // it).  Right behind a barrier a SIMD then has one wave with twelve MFMAs ready in registers while its partner waits for
-        // its first fragments, instead of two waves waiting for LDS with an idle matrix pipe (stamps: ~500 of ~2050 cycles per
-        // k-tile; MI355X_MICROARCH.md, two waves per SIMD, item 9).  Same MFMA order per accumulator: same bits.
-        struct Held { bf16x8 bh[2], bl[2], a2h, a2l, a3h, a3l; };
-        Held H0, H1;
-        auto late = [&](int kt, Held& cur, const Held& prev) {
-            wait_tile();
-            __builtin_amdgcn_s_barrier();
-            const unsigned char* st = smem + (kt % DMA_D) * DMA_STAGE;
-            bf16x8 a0h, a0l, a1h, a1l;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) frag(st + fb + j * 128, cur.bh[j], cur.bl[j]);
-            frag(st + fa, a0h, a0l);
-            __builtin_amdgcn_sched_barrier(0);
-            piece(kt + DMA_D - 1, 0); piece(kt + DMA_D - 1, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kt > 0) mma_group(std::integral_constant<int, 2>{}, prev.a2h, prev.a2l, prev.bh, prev.bl);
-            frag(st + fa + 128, a1h, a1l);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kt > 0) mma_group(std::integral_constant<int, 3>{}, prev.a3h, prev.a3l, prev.bh, prev.bl);
-            __builtin_amdgcn_sched_barrier(0);
-            piece(kt + DMA_D - 1, 2);
-            __builtin_amdgcn_sched_barrier(0);
-            frag(st + fa + 256, cur.a2h, cur.a2l);
-            mma_group(std::integral_constant<int, 0>{}, a0h, a0l, cur.bh, cur.bl);
-            __builtin_amdgcn_sched_barrier(0);
-            piece(kt + DMA_D - 1, 3);
-            __builtin_amdgcn_sched_barrier(0);
-            frag(st + fa + 384, cur.a3h, cur.a3l);
-            mma_group(std::integral_constant<int, 1>{}, a1h, a1l, cur.bh, cur.bl);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the held fragments are in registers before the stage is released
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        for (int kt = 0; kt < nkt; kt += 2) {
-            late(kt, H0, H1);
-            if (kt + 1 < nkt) late(kt + 1, H1, H0);
-        }
-        if ((nkt - 1) & 1) {
-            mma_group(std::integral_constant<int, 2>{}, H1.a2h, H1.a2l, H1.bh, H1.bl);
-            mma_group(std::integral_constant<int, 3>{}, H1.a3h, H1.a3l, H1.bh, H1.bl);
-        } else {
-            mma_group(std::integral_constant<int, 2>{}, H0.a2h, H0.a2l, H0.bh, H0.bl);
-            mma_group(std::integral_constant<int, 3>{}, H0.a3h, H0.a3l, H0.bh, H0.bl);
-        }
-    } else if (XPS_DMA_PAIR && DMA_D == 4) {
-        // TWO k-tiles per barrier: the ring is two half-rings of two stages; behind the barrier that ends pair P - 1 the eight
-        // pieces of pair P + 1 go out (into the stages pair P - 1 was read from) while pair P is multiplied -- 64 KiB in flight per
-        // CU for two k-tile times.  Halves the barriers (stamps of the one-k-tile form: 464 of ~2100 cycles per k-tile and wave at
-        // the barrier, mostly skew between the eight waves) and the fragment-latency bubbles behind them (the second k-tile's
-        // fragments are requested under the first one's last MFMAs).  Same MFMA order per accumulator: same bits.
-        for (int kt = 0; kt < nkt; kt += 2) {
-            DSTAMP(t0)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's pieces of k-tiles kt, kt + 1 have landed
-            DSTAMP(t1)
-            __builtin_amdgcn_s_barrier();                          // ... everybody's; and everybody is done reading kt - 2, kt - 1
-            DSTAMP(t2)
-            DSTAMP(t3)
-            const bool two = kt + 1 < nkt, more = kt + 2 < nkt, more2 = kt + 3 < nkt;      // (uniform)
-            const unsigned char* st0 = smem + (kt % DMA_D) * DMA_STAGE;
-            const unsigned char* st1 = smem + ((kt + 1) % DMA_D) * DMA_STAGE;
-            bf16x8 bh[2], bl[2], ah[2], al[2], ch[2], cl[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) frag(st0 + fb + j * 128, bh[j], bl[j]);
-            frag(st0 + fa, ah[0], al[0]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (more) { piece(kt + 2, 0); piece(kt + 2, 1); }
-            __builtin_amdgcn_sched_barrier(0);
-            // k-tile kt: row group i's six MFMAs under the requests of group i + 1 (group 3: of k-tile kt + 1's first fragments)
-            frag(st0 + fa + 128, ah[1], al[1]);
-            mma_group(std::integral_constant<int, 0>{}, ah[0], al[0], bh, bl);
-            __builtin_amdgcn_sched_barrier(0);
-            if (more) { piece(kt + 2, 2); piece(kt + 2, 3); }
-            __builtin_amdgcn_sched_barrier(0);
-            frag(st0 + fa + 256, ah[0], al[0]);
-            mma_group(std::integral_constant<int, 1>{}, ah[1], al[1], bh, bl);
-            __builtin_amdgcn_sched_barrier(0);
-            if (more2) { piece(kt + 3, 0); piece(kt + 3, 1); }
-            __builtin_amdgcn_sched_barrier(0);
-            frag(st0 + fa + 384, ah[1], al[1]);
-            mma_group(std::integral_constant<int, 2>{}, ah[0], al[0], bh, bl);
-            __builtin_amdgcn_sched_barrier(0);
-            if (more2) { piece(kt + 3, 2); piece(kt + 3, 3); }
-            __builtin_amdgcn_sched_barrier(0);
-            if (two) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) frag(st1 + fb + j * 128, ch[j], cl[j]);
-                frag(st1 + fa, ah[0], al[0]);
-            }
-            mma_group(std::integral_constant<int, 3>{}, ah[1], al[1], bh, bl);
-            __builtin_amdgcn_sched_barrier(0);
-            if (two) {
-                frag(st1 + fa + 128, ah[1], al[1]);
-                mma_group(std::integral_constant<int, 0>{}, ah[0], al[0], ch, cl);
-                __builtin_amdgcn_sched_barrier(0);
-                frag(st1 + fa + 256, ah[0], al[0]);
-                mma_group(std::integral_constant<int, 1>{}, ah[1], al[1], ch, cl);
-                __builtin_amdgcn_sched_barrier(0);
-                frag(st1 + fa + 384, ah[1], al[1]);
-                mma_group(std::integral_constant<int, 2>{}, ah[0], al[0], ch, cl);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_group(std::integral_constant<int, 3>{}, ah[1], al[1], ch, cl);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#ifdef XPS_DMA_STAMP
-            DSTAMP(t4)
-            s_wait += t1 - t0; s_bar += t2 - t1; s_dma += t3 - t2; s_mma += t4 - t3;
-#endif
-        }
-    } else
+    static_assert(DMA_D == 4, "the counted wait below leaves the eight pieces of two k-tiles in flight");
     for (int kt = 0; kt < nkt; ++kt) {
         DSTAMP(t0)
-        wait_tile();
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // this wave's pieces of k-tile kt have landed
         DSTAMP(t1)
         __builtin_amdgcn_s_barrier();                          // ... everybody's; and everybody is done reading k-tile kt - 1
         DSTAMP(t2)
-        if (!XPS_DMA_SPREAD) {
-#pragma unroll
-            for (int pc = 0; pc < 4; ++pc) piece(kt + DMA_D - 1, pc);
-        }
         DSTAMP(t3)
         const unsigned char* st = smem + (kt % DMA_D) * DMA_STAGE;
         bf16x8 bh[2], bl[2], ah[2], al[2];
@@ -297,14 +156,14 @@ __device__ inline void tn_dma_pipeline(f32x16 (&acc)[4][2], f32x16& cacc, const 
         for (int j = 0; j < 2; ++j) frag(st + fb + j * 128, bh[j], bl[j]);
         frag(st + fa, ah[0], al[0]);
         __builtin_amdgcn_sched_barrier(0);
-        if (XPS_DMA_SPREAD) { piece(kt + DMA_D - 1, 0); piece(kt + DMA_D - 1, 1); }
+        piece(kt + DMA_D - 1, 0); piece(kt + DMA_D - 1, 1);
         __builtin_amdgcn_sched_barrier(0);
         auto group = [&](auto I) {
             constexpr int i = decltype(I)::value;
             if (i + 1 < 4) frag(st + fa + (i + 1) * 128, ah[(i + 1) & 1], al[(i + 1) & 1]);
             mma_group(I, ah[i & 1], al[i & 1], bh, bl);
             __builtin_amdgcn_sched_barrier(0);
-            if (XPS_DMA_SPREAD && i < 2) {
+            if (i < 2) {
                 piece(kt + DMA_D - 1, 2 + i);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -435,58 +294,6 @@ __device__ inline void direct_dma_pipeline(f32x16 (&acc)[4][2], const float* __r
         fh = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
         fl = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
     };
-#ifndef XPS_DIRECT_MERGED
-#define XPS_DIRECT_MERGED 0
-#endif
-#if XPS_DIRECT_MERGED
-    // (Built and measured, not the default: NT 40960-row projection shape 299.5 / 303.0 us against 299.2 / 299.5 us for the
-    //  two-barrier form below, NN 279.9 / 279.7 against 283.1 / 286.5 us -- profiles/round4: the compiler already rotates the
-    //  two-barrier loop so that the refill burst sits among the last MFMAs of a stage, and the refill keeps a whole stage of lead.)
-    // ONE barrier per stage: "every piece of stage ks has landed" and "everybody is done reading stage ks - 1" are the same
-    // barrier when the refill of the freed buffer (stage ks + 1) is issued BEHIND it, spread over the MFMA groups of the first
-    // k-tile (two pieces per row group) -- stamps of the first form (refill of stage ks + 2 in one burst behind a second barrier):
-    // per 32-deep stage and wave 44 cycles waiting for data, 1199 in the two barriers, 697 issuing the burst with an idle matrix
-    // pipe, 2974 in reads + MFMAs (3072 is the floor per SIMD).
-#pragma unroll
-    for (int pc = 0; pc < 8; ++pc) piece(0, pc);
-    for (int ks = 0; ks < nks; ++ks) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's pieces of stage ks (the only ones in flight) have landed
-        __builtin_amdgcn_s_barrier();                              // ... everybody's; and everybody is done reading stage ks - 1
-        const unsigned char* sa = smem + (ks & 1) * STAGE;
-        const unsigned char* sb = sa + KC_IMG;
-        const bool more = ks + 1 < nks;                            // (no refill behind the last stage: nothing may land after the hand-back)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            bf16x8 bh[2], bl[2];
-            if (active) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if (BKX) frag_kx(sb, wn + 32 * j, t, bh[j], bl[j]);
-                    else frag_kc(sb, wn + 32 * j, t, bh[j], bl[j]);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (active) {
-                    bf16x8 ah, al;
-                    frag_kc(sa, wm + 32 * i, t, ah, al);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[j], acc[i][j], 0, 0, 0);
-                    }
-                }
-                if (t == 0 && more) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    piece(ks + 1, 2 * i); piece(ks + 1, 2 * i + 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-#else
 #pragma unroll
     for (int pc = 0; pc < 8; ++pc) piece(0, pc);
 #pragma unroll
@@ -539,7 +346,6 @@ __device__ inline void direct_dma_pipeline(f32x16 (&acc)[4][2], const float* __r
         unsigned long long* o = g_dma_stamp + ((blockIdx.x * 8 + wave) & 4095) * 4;
         o[0] = z_wait; o[1] = z_bar + z_bar2; o[2] = z_dma; o[3] = z_mma;
     }
-#endif
 #endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();

@@ -6,13 +6,8 @@
 
 namespace xps_tile {
 
-#ifndef XPS_BKT
-#define XPS_BKT 16
-#endif
-#ifndef XPS_GEMM_WAVES
-#define XPS_GEMM_WAVES 1
-#endif
-constexpr int BM = 128, BN = 128, BKT = XPS_BKT, LDT = 132;
+constexpr int BM = 128, BN = 128, BKT = 16, LDT = 132;
+constexpr int GEMM_WAVES = 1;        // second argument of the tile kernels' __launch_bounds__
 
 #ifdef XPS_GSTAMP
 // diagnostic build only: per-wave cycle shares of the k loop (written to a buffer no kernel reads)

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 #include "xps_common.h"
 #include "xps_gemm_tile.h"
+#include "xps_switches.h"
 using xps_tile::bf16x4;
 using xps_tile::bf16x8;
 using xps_tile::bf_split;
@@ -40,10 +41,7 @@ bool xps_internal_gru_cluster_ximg_ok(int B, int H, int ndir);
 namespace {
 
 constexpr int GBM = 16;   // trials per workgroup
-#ifndef XPS_GRU_BF_WAVES
-#define XPS_GRU_BF_WAVES 8
-#endif
-constexpr int GRU_BF_WAVES = XPS_GRU_BF_WAVES;   // waves per workgroup of the H = 128 bf16 recurrence kernels
+constexpr int GRU_BF_WAVES = 8;   // waves per workgroup of the H = 128 bf16 recurrence kernels
 
 struct GruFwdParams {
     const float* gi;
@@ -425,17 +423,9 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_fwd_resident_kernel(GruFwdPara
     // LDS row strides of 8 dwords (mod 64): the b128 fragment reads (16 trials x 4 k-quarters; lane groups {0-3,12-15,20-27}, ...:
     // MI355X_MICROARCH.md, LDS) then touch 16 distinct 4-bank groups per service cycle.  (4 (mod 64), the round-1 value, put
     // trials 11 / kq 1 and 12 / kq 0 on the same banks: 40 % of the LDS-active cycles were conflicts.)
-#ifdef XPS_GRU_OLD_PAD
-    constexpr int NT = H / 16, TPW = NT / NW, NC = H / 16, LDH = H + 4;
-#else
     constexpr int NT = H / 16, TPW = NT / NW, NC = H / 16, LDH = H + 8;
-#endif
     static_assert(NT % NW == 0, "hidden tiles must divide among the waves");
-#ifdef XPS_GRU_OLD_PAD
-    constexpr int NCB = H / 32, LDB = H + 8;
-#else
     constexpr int NCB = H / 32, LDB = H + 16;  // BF: 32-wide k chunks; bf16 row stride (conflict-free b128 reads)
-#endif
     constexpr int NST = TPW * 6;               // 16-byte stores per lane and step: h, r, z, n, q (, dropped h) per tile
     __shared__ __attribute__((aligned(16))) float hs[2][GBM][LDH];
     __shared__ __attribute__((aligned(16))) __bf16 hsb[BF ? 2 : 1][2][BF ? GBM : 1][BF ? LDB : 8];   // [buffer][hi, lo][trial][k]
@@ -683,17 +673,9 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_fwd_resident_kernel(GruFwdPara
 template <int H, bool BF = false, int NW = 4>
 __global__ __launch_bounds__(NW * 64, 1) void gru_bwd_resident_kernel(GruBwdParams p) {
     constexpr int NTHR = NW * 64;
-#ifdef XPS_GRU_OLD_PAD
-    constexpr int NT = H / 16, TPW = NT / NW, NC = 3 * H / 16, LDG = 3 * H + 4, LDC = H + 4;
-#else
     constexpr int NT = H / 16, TPW = NT / NW, NC = 3 * H / 16, LDG = 3 * H + 8, LDC = H + 8;   // strides: 8 dwords (mod 64), see the forward kernel
-#endif
     static_assert(NT % NW == 0, "hidden tiles must divide among the waves");
-#ifdef XPS_GRU_OLD_PAD
-    constexpr int NCB = 3 * H / 32, LDGB = 3 * H + 8;
-#else
     constexpr int NCB = 3 * H / 32, LDGB = 3 * H + 16;    // BF: 32-wide k chunks; bf16 row stride of the gate gradients
-#endif
     constexpr int H4 = H / 4, GPT = GBM * H4 / NTHR;       // float4 groups of the 16 x H tile per thread
     __shared__ __attribute__((aligned(16))) float G[BF ? 1 : GBM][BF ? 4 : LDG];
     __shared__ __attribute__((aligned(16))) __bf16 Gb[2][BF ? GBM : 1][BF ? LDGB : 8];      // BF: [hi, lo][trial][k]
@@ -1220,10 +1202,7 @@ __global__ void transpose_batched_kernel(TransposeBatch tb, int rows, int cols) 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // XPS_GRU_STEP_PATH=0 forces the streaming persistent kernels for H > 128 (A/B comparisons)
-inline bool use_step_path() {
-    static const bool on = [] { const char* e = getenv("XPS_GRU_STEP_PATH"); return !(e && e[0] == '0'); }();
-    return on;
-}
+inline bool use_step_path() { return xps_sw::on(xps_sw::GRU_STEP_PATH); }
 
 }  // namespace
 

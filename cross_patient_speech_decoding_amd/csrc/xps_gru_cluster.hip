@@ -35,6 +35,7 @@
 #include "xps_common.h"
 #include <atomic>
 #include "xps_gemm_tile.h"
+#include "xps_switches.h"
 using xps_tile::bf16x4;
 using xps_tile::bf16x8;
 using xps_tile::bf_split;
@@ -186,26 +187,6 @@ __device__ inline void cl_dma4(const unsigned char* gsrc, unsigned l0, unsigned 
                  : "=&s"(keep) : "v"(gsrc), "s"(l0), "s"(l1), "s"(l2), "s"(l3));
 }
 
-// ALTERNATIVE exchange-row layout of the forward kernel (bf16x3 mode, compile-time: -DXPS_CL_FWD_PLANES=0; round 4): XPS_FMT_SPLIT4
-// groups (16 B: hi[0..3] | lo[0..3] of four consecutive k) instead of a hi plane and a lo plane, so that a gate-wave lane stores
-// ONE 16-byte vector and a member's 32 units are one FULL 128-byte line of the row (the planes: two 8-byte stores, two half lines).
-// An MFMA fragment needs the hi halves of TWO neighbouring groups: inside every 128-byte line (32 k = 8 groups) the row holds the
-// four EVEN groups first, then the four odd ones -- the producer stores group g of a line at slot (g & 1) * 4 + (g >> 1)
-// (cl_xslot), the DMA pieces copy lines as they lie; the k-quarter kq of a chunk reads groups 2 kq, 2 kq + 1 at line + 16 kq and
-// + 64 (per instruction the bank pattern of a plane read: conflict-free) and regroups the halves in registers.
-// Bit-identical, all cluster tests green -- and measured LEVEL on one box, three interleaved runs each (tools/bench_gru.py with
-// XPS_LIB_OVERRIDE): forward with saved gates 591-597 us both ways, forward without 478 vs 464 us (slower), configs[3] step 6.51-6.52
-// vs 6.49-6.53 ms.  The same layout in the BPTT kernel cost its launches 5-8 % (the contraction waves, which pace it, wait for
-// both reads of a fragment and regroup them before the first MFMA), as did a per-lane group permutation on the source side of the
-// DMA pieces.  The planes stay the default.
-__device__ inline unsigned cl_xslot(unsigned g) { return ((g & 1u) << 2) | ((g & 7u) >> 1); }
-#ifndef XPS_CL_BWD_LINEPLANAR
-#define XPS_CL_BWD_LINEPLANAR 0     // exchange rows of the 1-D BPTT kernel (bf16x3): 0 = hi plane | lo plane, 1 = line-planar (see its epilogue; measured slower)
-#endif
-#ifndef XPS_CL_FWD_PLANES
-#define XPS_CL_FWD_PLANES 1        // 0: the forward kernel's exchange rows as XPS_FMT_SPLIT4 groups (see above; A/B builds)
-#endif
-
 // image exchange (XIMG): lane 8 l + s of a DMA piece writes LDS slot s of line l and fetches global group 2 s (s < 4) or
 // 2 (s - 4) + 1 of that line: the standard XPS_FMT_SPLIT4 row in memory becomes the even | odd arrangement in LDS
 __device__ inline int cl_ximg_lane(int lane) { return (lane & ~7) | ((lane & 3) * 2 + ((lane >> 2) & 1)); }
@@ -326,14 +307,13 @@ struct ClFwd {
 // (its exchange rows were complete before the last barrier), poll of the flags of round it + 2.
 // XIMG (bf16x3 mode, H == KP, B % 32 == 0, training): the exchange buffer IS the XPS_FMT_SPLIT4 image of y_ext (ClFwd::y_split) -- a
 // member publishes h_t by ONE 16-byte store per lane into slot t + 1 of the image (standard group order), the operand image of the
-// next step is moved from the rows of that slot by LDS-DMA pieces whose lanes pick the groups in even / odd order (cl_ximg_lane; the
-// fragment reads are those of the XPS_CL_FWD_PLANES = 0 layout), and the weight-gradient GEMMs read h_prev from the same image: no
+// next step is moved from the rows of that slot by LDS-DMA pieces whose lanes pick the groups in even / odd order (cl_ximg_lane; a
+// fragment is regrouped from the hi and lo halves of two neighbouring groups), and the weight-gradient GEMMs read h_prev from the same image: no
 // ring buffer traffic of its own, one store per lane and round fewer, and no xps_split4_f32 pass over y_ext afterwards.
 template <int KSPLIT, bool BF, bool XIMG = false>
 __global__ __launch_bounds__(512, 2) void gru_cluster_fwd_kernel(ClFwd p) {
     static_assert(KSPLIT == 2, "the cluster kernels cover 256 < H <= 512");
     static_assert(!XIMG || BF, "the image exchange exists in bf16x3 mode only");
-    constexpr bool SPLITROWS = XIMG || !XPS_CL_FWD_PLANES;       // exchange rows / LDS image as split4 groups (even | odd per line)
     using Cf = ClCfg<KSPLIT, BF, 1>;
     constexpr int KP = Cf::KP, TS = Cf::TS, PS = Cf::PS, TILE = Cf::TILE_BYTES;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -429,11 +409,11 @@ __global__ __launch_bounds__(512, 2) void gru_cluster_fwd_kernel(ClFwd p) {
                 // 16 steps (tile, chunk); the fragments of step i + 2 are requested before the MFMAs of step i (a ring of three,
                 // pinned with scheduling barriers: left alone the scheduler issues the reads of two steps right in front of
                 // their 18 MFMAs and exposes the LDS latency eight times per round)
-                // (exchange rows are XPS_FMT_SPLIT4 groups; a line holds its even groups, then its odd ones: cl_xslot)
-                const unsigned char* rp0 = !SPLITROWS ? tb + n * TS + (kbase + 8 * kq) * 2 : tb + n * TS + kh * PS + kq * 16;
+                // (XIMG: the LDS image holds XPS_FMT_SPLIT4 groups; a line holds its even groups, then its odd ones: cl_ximg_lane)
+                const unsigned char* rp0 = !XIMG ? tb + n * TS + (kbase + 8 * kq) * 2 : tb + n * TS + kh * PS + kq * 16;
                 bf16x8 bh[3], bl[3];
                 auto frag = [&](int i, bf16x8& h8, bf16x8& l8) {
-                    if constexpr (!SPLITROWS) {
+                    if constexpr (!XIMG) {
                         const unsigned char* rp = rp0 + (i >> 3) * 16 * TS + (i & 7) * 64;
                         h8 = *reinterpret_cast<const bf16x8*>(rp);
                         l8 = *reinterpret_cast<const bf16x8*>(rp + PS);
@@ -540,16 +520,11 @@ __global__ __launch_bounds__(512, 2) void gru_cluster_fwd_kernel(ClFwd p) {
         const int b = m_base + 32 * rn + gtr;
         const int bc = b < B ? b : B - 1;
         const float* gp = gi + ((long long)t * B + bc) * 3 * H + juc;
-#ifdef XPS_CL_ABL_NOLOAD
-        in.gr = (f32x4){0.1f, 0.2f, 0.3f, 0.4f}; in.gz = in.gr; in.gn = in.gr; in.hp = (u32x4){0u, 0u, 0u, 0u};
-        (void)gp; (void)slot_prev;
-#else
         in.gr = *reinterpret_cast<const f32x4*>(gp);
         in.gz = *reinterpret_cast<const f32x4*>(gp + H);
         in.gn = *reinterpret_cast<const f32x4*>(gp + 2 * H);
         // own previous state (fp32), written by this lane one step ago (or by the init kernel)
         in.hp = __builtin_amdgcn_raw_buffer_load_b128(yr, (unsigned)((((long long)slot_prev * B + bc) * ldy + dir * H + juc) * 4), 0, AUX_SC1);
-#endif
     };
     // gates + hidden update of round (sn, rn) for this lane's trial and four units; exchange rows of the next step (every lane
     // stores: rows of pad trials / pad units carry zeros), then the outputs: h_t and (training) the saved gates, 1 or 5 stores,
@@ -579,24 +554,16 @@ __global__ __launch_bounds__(512, 2) void gru_cluster_fwd_kernel(ClFwd p) {
         } else if (sn + 1 < T) {
             const unsigned row = (unsigned)((((sn + 1) & 1) * p.ndir + dir) * p.Bp + b);
             if constexpr (BF) {
-                // (SPLITROWS: ONE 16-byte store per lane, hi[0..3] | lo[0..3] of its four units; a member's 32 units = one full line)
-                if constexpr (!SPLITROWS) {
-                    bf16x4 sh, sl;
+                bf16x4 sh, sl;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) { __bf16 x, c; bf_split(o[i], x, c); sh[i] = x; sl[i] = c; }
-                    const unsigned off = row * (unsigned)(KP * 4) + (unsigned)ju * 2u;
-                    if (fast) {
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sh), xr, off, 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sl), xr, off + KP * 2, 0, 0);
-                    } else {
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sh), xr, off, 0, AUX_SC1);
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sl), xr, off + KP * 2, 0, AUX_SC1);
-                    }
+                for (int i = 0; i < 4; ++i) { __bf16 x, c; bf_split(o[i], x, c); sh[i] = x; sl[i] = c; }
+                const unsigned off = row * (unsigned)(KP * 4) + (unsigned)ju * 2u;
+                if (fast) {
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sh), xr, off, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sl), xr, off + KP * 2, 0, 0);
                 } else {
-                    const u32x4 sp = __builtin_bit_cast(u32x4, split4_pack(o));
-                    const unsigned off = row * (unsigned)(KP * 4) + ((unsigned)ju & ~31u) * 4u + cl_xslot((unsigned)ju >> 2) * 16u;
-                    if (fast) __builtin_amdgcn_raw_buffer_store_b128(sp, xr, off, 0, 0);
-                    else __builtin_amdgcn_raw_buffer_store_b128(sp, xr, off, 0, AUX_SC1);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sh), xr, off, 0, AUX_SC1);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sl), xr, off + KP * 2, 0, AUX_SC1);
                 }
             } else {
                 const unsigned off = row * (unsigned)(KP * 4) + (unsigned)ju * 4u;
@@ -681,9 +648,7 @@ __global__ __launch_bounds__(512, 2) void gru_cluster_fwd_kernel(ClFwd p) {
         CL_FENCE();
         if (it + 2 < it_end) {
             epi_load(s_n2, r_n2, ein[prv]);                 // (the slot the gate math above has just released)
-#ifndef XPS_CL_ABL_NOLOAD
             younger += 4;
-#endif
         }
         CL_FENCE();
         CL_STAMP(sb3)
@@ -745,15 +710,11 @@ __global__ void gru_cluster_init_kernel(const float* __restrict__ h0, float* __r
         if (!xbuf) continue;                               // (image exchange: slot_h0 of y_split, written above, is the first operand)
         unsigned char* row = reinterpret_cast<unsigned char*>(xbuf) + ((long long)dir * Bp + b) * KP * 4;
         if constexpr (BF) {
-            if (XPS_CL_FWD_PLANES) {
-                bf16x4 sh, sl;
+            bf16x4 sh, sl;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { __bf16 a, c; bf_split(v[e], a, c); sh[e] = a; sl[e] = c; }
-                *reinterpret_cast<bf16x4*>(row + k * 2) = sh;
-                *reinterpret_cast<bf16x4*>(row + KP * 2 + k * 2) = sl;
-            } else {
-                *reinterpret_cast<f32x4*>(row + (k & ~31) * 4 + cl_xslot((unsigned)k >> 2) * 16) = split4_pack(v);
-            }
+            for (int e = 0; e < 4; ++e) { __bf16 a, c; bf_split(v[e], a, c); sh[e] = a; sl[e] = c; }
+            *reinterpret_cast<bf16x4*>(row + k * 2) = sh;
+            *reinterpret_cast<bf16x4*>(row + KP * 2 + k * 2) = sl;
         } else {
             *reinterpret_cast<f32x4*>(row + k * 4) = v;
         }
@@ -996,26 +957,7 @@ __global__ __launch_bounds__(512, 2) void gru_cluster_bwd_kernel(ClBwd p) {
                     bf16x4 sh, sl;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { __bf16 a, c; bf_split((*gsrc[g])[i], a, c); sh[i] = a; sl[i] = c; }
-                    if (XPS_CL_BWD_LINEPLANAR) {
-                        // LINE-PLANAR row (alternative, compile time): every 128-byte line holds the hi halves of its 32 k (64 B), then
-                        // their lo halves (64 B).  The two lanes of a unit octet swap one half (DPP) so that the even lane stores
-                        // hi[0..7] and the odd lane lo[0..7] as ONE 16-byte vector each: three stores per lane and round instead of
-                        // six, a member's 32 units of a gate = one FULL line per trial (the planes: two half lines), and a fragment
-                        // register is still one contiguous 16-byte read (no regrouping in the contraction waves).  Bit-identical,
-                        // all cluster tests green -- and SLOWER on one box, three interleaved runs each (tools/bench_gru.py with
-                        // XPS_LIB_OVERRIDE): BPTT launch 812 / 812 / 829 us against 780 / 778 / 766 us with the planes.  The third
-                        // exchange layout with 16-byte stores that loses 5-8 % in this kernel (XPS_CL_FWD_PLANES above).
-                        const bool odd = (guq & 1) != 0;
-                        const u32x2 mine_h = __builtin_bit_cast(u32x2, sh), mine_l = __builtin_bit_cast(u32x2, sl);
-                        const u32x2 give = odd ? mine_h : mine_l;
-                        u32x2 got;
-                        got[0] = (unsigned)__shfl_xor((int)give[0], 1);
-                        got[1] = (unsigned)__shfl_xor((int)give[1], 1);
-                        const u32x4 v = odd ? (u32x4){got[0], got[1], mine_l[0], mine_l[1]} : (u32x4){mine_h[0], mine_h[1], got[0], got[1]};
-                        const unsigned xo = base + ((unsigned)ju & ~31u) * 4u + (odd ? 64u : 0u) + (unsigned)(guq >> 1) * 16u;
-                        if (fast) __builtin_amdgcn_raw_buffer_store_b128(v, xr, xo, 0, 0);
-                        else __builtin_amdgcn_raw_buffer_store_b128(v, xr, xo, 0, AUX_SC1);
-                    } else if (fast) {
+                    if (fast) {
                         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sh), xr, base + (unsigned)ju * 2u, 0, 0);
                         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sl), xr, base + KP * 2 + (unsigned)ju * 2u, 0, 0);
                     } else {
@@ -1134,10 +1076,9 @@ __global__ __launch_bounds__(512, 2) void gru_cluster_bwd_kernel(ClBwd p) {
                                 bh = __builtin_shufflevector(ga, gb, 0, 1, 2, 3, 8, 9, 10, 11);
                                 bl = __builtin_shufflevector(ga, gb, 4, 5, 6, 7, 12, 13, 14, 15);
                             } else {
-                                const unsigned char* rp = XPS_CL_BWD_LINEPLANAR ? tb + (tt * 16 + n) * TS + kh * PS + c * 128 + kq * 16
-                                                                                : tb + (tt * 16 + n) * TS + (kbase + 32 * c + 8 * kq) * 2;
+                                const unsigned char* rp = tb + (tt * 16 + n) * TS + (kbase + 32 * c + 8 * kq) * 2;
                                 bh = *reinterpret_cast<const bf16x8*>(rp);
-                                bl = *reinterpret_cast<const bf16x8*>(rp + (XPS_CL_BWD_LINEPLANAR ? 64 : PS));
+                                bl = *reinterpret_cast<const bf16x8*>(rp + PS);
                             }
                             acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.wl[gg][c], bh, acc[tt], 0, 0, 0);
                             acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.wh[gg][c], bl, acc[tt], 0, 0, 0);
@@ -1361,18 +1302,8 @@ struct ClBwd2 {
     int split_out;
 };
 
-#if defined(XPS_CL2_NT_LOADS)
-#define CL2_STREAM_LOAD(ptr) __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ptr))
-#else
 #define CL2_STREAM_LOAD(ptr) (*reinterpret_cast<const f32x4*>(ptr))
-#endif
-#if defined(XPS_CL2_NT_STORES)
-constexpr int CL2_AUX_STREAM = 2;           // raw buffer builtins: bit 1 = nt
-#elif defined(XPS_CL2_SC1_STORES)
-constexpr int CL2_AUX_STREAM = 16;          // write-through, line dropped from L2
-#else
-constexpr int CL2_AUX_STREAM = 0;
-#endif
+constexpr int CL2_AUX_STREAM = 0;           // (nt / sc1 flavours of the streamed loads and stores: profiles/round3/cache_policy_variants.txt)
 constexpr int C2_RT = 16;                   // trials per round
 constexpr int C2_IMG = C2_RT * 1536;        // one operand image
 constexpr int C2_NIMG = 4;                  // image ring
@@ -1951,17 +1882,7 @@ int cl_num_cus() {
 }
 
 // mode: 0 = off (per-step GEMM kernels of xps_gru.hip), 1 = cluster kernels one step per launch, 2 = persistent (default)
-int g_cluster_mode = -1;
-int cl_mode() {
-    if (g_cluster_mode < 0) {
-        const char* e = getenv("XPS_GRU_CLUSTER");
-        int m = 2;
-        if (e && (!strcmp(e, "off") || !strcmp(e, "0"))) m = 0;
-        else if (e && (!strcmp(e, "steps") || !strcmp(e, "1"))) m = 1;
-        g_cluster_mode = m;
-    }
-    return g_cluster_mode;
-}
+int cl_mode() { return (int)xps_sw::get(xps_sw::GRU_CLUSTER); }
 
 ClPlan cl_plan(int B, int H, int ndir) {
     ClPlan pl;
@@ -1969,7 +1890,7 @@ ClPlan cl_plan(int B, int H, int ndir) {
     if (cl_mode() == 0 || H <= 256 || H > 512 || (H % 4) != 0 || B < 128) return pl;
     int cus = cl_num_cus();
     {   // diagnostic: plan for fewer CUs than the device has (how the launch time scales with the CUs that take part: DESIGN.md 4.5)
-        static const int cap = [] { const char* e = getenv("XPS_GRU_CL_CUS"); return e ? atoi(e) : 0; }();
+        const int cap = (int)xps_sw::get(xps_sw::GRU_CL_CUS);
         if (cap > 0 && cap < cus) cus = cap;
     }
     pl.KSPLIT = H > 256 ? 2 : 1;
@@ -2007,11 +1928,7 @@ ClPlan cl_plan(int B, int H, int ndir) {
 // 3.4 GB (PMC): both kernels move their bytes at ~3.5-4 TB/s and NONE of the exchanged bytes is served from the XCD's L2 (they
 // are consumed a step after they were written: 25 MB of stream traffic per XCD later), so the second hand-off of the 2-D grid
 // (the partial-sum quarters: +1 GB written and re-fetched) costs what its three-fold smaller LDS-DMA ingest saves.  DESIGN.md 4.5.
-int g_cl2 = -1;
-bool cl2_enabled() {
-    if (g_cl2 < 0) { const char* e = getenv("XPS_GRU_CL2"); g_cl2 = (e && e[0] == '1') ? 1 : 0; }
-    return g_cl2 != 0;
-}
+bool cl2_enabled() { return xps_sw::on(xps_sw::GRU_CL2); }
 struct ClPlan2 {
     bool ok;
     int nblk, Mc, NR, Bp, grid;
@@ -2067,17 +1984,11 @@ int cl_resident(K kernel, int lds, int kind, int bf) {
     return v;
 }
 
-// XPS_GRU_XIMG=0: the forward kernel keeps its ring buffer even when it writes the image of y_ext (A/B; read per call)
-bool cl_ximg_enabled() {
-    const char* e = getenv("XPS_GRU_XIMG");
-    return !(e && e[0] == '0');
-}
+// XPS_GRU_XIMG=0: the forward kernel keeps its ring buffer even when it writes the image of y_ext (A/B)
+bool cl_ximg_enabled() { return xps_sw::on(xps_sw::GRU_XIMG); }
 
-// XPS_GRU_XOUT=1: the 1-D BPTT kernel reads its exchange rows from its own outputs (A/B; read per call)
-bool cl_xout_enabled() {
-    const char* e = getenv("XPS_GRU_XOUT");
-    return e && e[0] == '1';
-}
+// XPS_GRU_XOUT=1: the 1-D BPTT kernel reads its exchange rows from its own outputs (A/B)
+bool cl_xout_enabled() { return xps_sw::on(xps_sw::GRU_XOUT); }
 
 unsigned* cl_sticky() {
     const int dev = cl_device();
@@ -2314,13 +2225,13 @@ extern "C" int xps_debug_read_cluster_stamps(unsigned long long* host, int n) {
 
 extern "C" int xps_set_gru_cluster_mode(int mode) {
     if (mode < 0 || mode > 2) { xps_set_error("xps_set_gru_cluster_mode: mode must be 0 (off), 1 (one step per launch) or 2 (persistent)"); return XPS_E_INVALID; }
-    g_cluster_mode = mode;
+    xps_sw::store(xps_sw::GRU_CLUSTER, mode);
     return XPS_OK;
 }
 extern "C" int xps_get_gru_cluster_mode(void) { return cl_mode(); }
 extern "C" int xps_set_gru_bptt_grid(int two_dimensional) {
     if (two_dimensional != 0 && two_dimensional != 1) { xps_set_error("xps_set_gru_bptt_grid: 0 (1-D cluster kernel) or 1 (4 x 4 grid)"); return XPS_E_INVALID; }
-    g_cl2 = two_dimensional;
+    xps_sw::store(xps_sw::GRU_CL2, two_dimensional);
     return XPS_OK;
 }
 extern "C" int xps_get_gru_bptt_grid(void) { return cl2_enabled() ? 1 : 0; }

@@ -7,12 +7,12 @@ fallback: a non-CUDA tensor raises.
 Internal activation layout is TIME-MAJOR: (T, B, features).
 """
 import ctypes as C
-import os
 from typing import NamedTuple
 
 import torch
 
 from .._dev import need_gpu as _need_gpu, ptr as _ptr, ptr_array as _ptr_array, stream as _stream, workspace as _ws  # noqa: F401
+from .. import _switches
 from .._lib import TnProblem, call, lib, rowmap
 
 _f32 = torch.float32
@@ -38,9 +38,9 @@ _memo_values = {}
 
 
 def _memo(key, compute):
-    """compute() once per key, for answers of the library that depend on nothing but the key: each use names in its key all
-    they depend on, library state (precision, cluster mode, BPTT grid) included.  Bounded: beyond 4096 keys nothing more is
-    kept.  _memo.clear() forgets everything."""
+    """compute() once per key, for answers that depend on nothing but the key and the switches: every _switches.set forgets
+    everything (as does _memo.clear()), and each use names in its key the library state that has a setter of its own
+    (precision, cluster mode, BPTT grid).  Bounded: beyond 4096 keys nothing more is kept."""
     v = _memo_values.get(key)
     if v is None:
         v = compute()
@@ -50,6 +50,7 @@ def _memo(key, compute):
 
 
 _memo.clear = _memo_values.clear
+_switches.on_change(_memo_values.clear)
 
 
 # --------------------------------------------------------------------------- #
@@ -118,7 +119,7 @@ def gemm_tn_grouped(problems, device, stream=None):
 # whatever the main stream runs next; the main stream re-joins when the autograd engine finishes the pass.
 # Only done when the results land straight in .grad buffers (DIRECT_GRAD): nothing on the main stream may
 # consume them before the join.  Deterministic: stream order does not change any reduction order.
-OVERLAP_WEIGHT_GRADS = os.environ.get('XPS_OVERLAP_WGRAD', '1') != '0'
+# XPS_OVERLAP_WGRAD=0: everything on the main stream.
 _side_streams = {}
 _side_pending = set()
 
@@ -127,7 +128,7 @@ def _low_priority_stream(idx):
     """Side stream BELOW the default priority (torch only offers default / high): when a CU frees up, kernels of
     the critical path are dispatched first; measured without it, tiny main-stream kernels queued up to 100 us
     behind the side stream's GEMM blocks."""
-    if os.environ.get('XPS_SIDE_PRIORITY') == 'default':       # (diagnostic: tools/graph_probe.py -- what a hipGraph replay does to the side work)
+    if _switches.get('XPS_SIDE_PRIORITY') == 'default':       # (diagnostic: tools/graph_probe.py -- what a hipGraph replay does to the side work)
         return torch.cuda.Stream(device=idx)
     handle = C.c_void_p()
     with torch.cuda.device(idx):
@@ -151,7 +152,7 @@ def _launch_weight_grads(fn, device, tensors, direct):
     stream) and returns the temporaries it allocated.  Runs it on the side stream when allowed.  The kernels take the
     stream as a C-ABI argument, so torch's current stream is never switched (the context manager and one
     record_stream per operand cost ~30 us of host time per call site; the operands are kept alive until the join)."""
-    if not (OVERLAP_WEIGHT_GRADS and direct):
+    if not (_switches.get('XPS_OVERLAP_WGRAD') and direct):
         fn(None)
         return
     idx = device.index if device.index is not None else torch.cuda.current_device()
@@ -309,18 +310,17 @@ def set_gru_cluster_mode(name):
 
 
 def fused_dropout_supported(T, B, H, ndir):
-    """The recurrence kernels of this shape apply the inter-layer dropout themselves (XPS_FUSED_DROPOUT=0: never; the switch
-    is read when a shape is first asked about: _memo.clear() after changing it)."""
-    return _memo(('fused_drop', T, B, H, ndir), lambda: os.environ.get('XPS_FUSED_DROPOUT', '1') != '0'
+    """The recurrence kernels of this shape apply the inter-layer dropout themselves (XPS_FUSED_DROPOUT=0: never)."""
+    return _memo(('fused_drop', T, B, H, ndir), lambda: bool(_switches.get('XPS_FUSED_DROPOUT'))
                  and bool(lib().xps_gru_seq_fused_dropout_supported(T, B, H, ndir)))
 
 
 def split4_supported(T, B, H, ndir):
     """The BPTT kernels of this shape can write dgi / dghn as XPS_FMT_SPLIT4 groups (include/xps.h) in the current precision
     mode: their readers (weight-gradient and input-gradient GEMMs) then stage them without conversion arithmetic, same bits.
-    XPS_SPLIT4=0: never (read when a shape is first asked about in a library state: _memo.clear() after changing it)."""
+    XPS_SPLIT4=0: never."""
     key = ('split4', T, B, H, ndir, lib().xps_get_gemm_precision(), lib().xps_get_gru_cluster_mode())
-    return _memo(key, lambda: os.environ.get('XPS_SPLIT4', '1') != '0' and bool(lib().xps_gru_seq_bwd_split4_supported(T, B, H, ndir)))
+    return _memo(key, lambda: bool(_switches.get('XPS_SPLIT4')) and bool(lib().xps_gru_seq_bwd_split4_supported(T, B, H, ndir)))
 
 
 def split4_wanted(T, B, H, ndir):
@@ -375,7 +375,7 @@ def hprev_split_wanted(T, B, H, ndir, split4=None):
     configs[3]'s layer 1 1.07-1.2 ms -> 0.95 ms (tools/bench_wgrad_group.py) for a 0.37-GB pass.  XPS_HPREV_SPLIT=0: never.
     split4: split4_wanted of this shape, where the caller has it (gru_layer_plan)."""
     return ((split4_wanted(T, B, H, ndir) if split4 is None else split4) and (ndir * H) % 4 == 0 and T * B >= 4096 and H % 256 == 0
-            and os.environ.get('XPS_HPREV_SPLIT', '1') != '0' and os.environ.get('XPS_GEMM_DMA', '1') != '0')
+            and bool(_switches.get('XPS_HPREV_SPLIT')) and bool(_switches.get('XPS_GEMM_DMA')))
 
 
 def fwd_ysplit_wanted(T, B, H, ndir, hprev=None):
@@ -384,7 +384,7 @@ def fwd_ysplit_wanted(T, B, H, ndir, hprev=None):
     H = 512, no pad trials): the image replaces the ring buffer's stores, and the xps_split4_f32 pass over y_ext in the backward
     (65 us and 0.34 GB per layer at configs[3]'s shape) is gone.  XPS_FWD_YSPLIT=0: the pass.  hprev: hprev_split_wanted of this
     shape, where the caller has it."""
-    return (os.environ.get('XPS_FWD_YSPLIT', '1') != '0' and (hprev_split_wanted(T, B, H, ndir) if hprev is None else hprev)
+    return (bool(_switches.get('XPS_FWD_YSPLIT')) and (hprev_split_wanted(T, B, H, ndir) if hprev is None else hprev)
             and bool(lib().xps_gru_seq_fwd_image_exchange_supported(T, B, H, ndir)))
 
 
@@ -395,7 +395,7 @@ def fwd_images_wanted(T, B, H, ndir, hprev=None):
     serial profile: split4 passes 192 -> 0 us, forward kernels 1359 -> 1541 us per step; headline 6.60 vs 6.61 ms): an extra 1-KiB
     store instruction per gate wave and round goes through the per-CU vector-memory pipe that paces the cluster kernels,
     at the price the separate pass pays at HBM speed.  Not the default.  hprev: as in fwd_ysplit_wanted."""
-    return (os.environ.get('XPS_FWD_IMAGES', '0') == '1' and (hprev_split_wanted(T, B, H, ndir) if hprev is None else hprev)
+    return (bool(_switches.get('XPS_FWD_IMAGES')) and (hprev_split_wanted(T, B, H, ndir) if hprev is None else hprev)
             and bool(lib().xps_gru_seq_fwd_images_supported(T, B, H, ndir)))
 
 
@@ -531,7 +531,7 @@ FMT_X_SPLIT4, FMT_Y_SPLIT4 = 1, 2
 
 def split4_mode():
     """XPS_FMT_SPLIT4 operands are in use: bf16x3 product mode and not switched off (XPS_SPLIT4=0)."""
-    return lib().xps_get_gemm_precision() == 1 and os.environ.get('XPS_SPLIT4', '1') != '0'
+    return lib().xps_get_gemm_precision() == 1 and bool(_switches.get('XPS_SPLIT4'))
 
 
 def layer_output_split4_ok(T, B, H, ndir, drop_p):
@@ -545,8 +545,8 @@ def layer_output_split4_ok(T, B, H, ndir, drop_p):
 def _presplit_weights_ok(rows, In, H3):
     """Pre-splitting W_ih (one small launch per matrix and forward pass) pays when the projection / input-gradient GEMMs
     that read it are large (configs[3] layer 1: 40960 x 1536 x 1024); XPS_SPLIT4_WEIGHTS=0: never."""
-    return (split4_mode() and In % 4 == 0 and rows >= 4096 and In * H3 >= int(os.environ.get('XPS_SPLIT4_WEIGHTS_MIN', 1 << 19))
-            and os.environ.get('XPS_SPLIT4_WEIGHTS', '1') != '0')
+    return (split4_mode() and In % 4 == 0 and rows >= 4096 and In * H3 >= _switches.get('XPS_SPLIT4_WEIGHTS_MIN')
+            and bool(_switches.get('XPS_SPLIT4_WEIGHTS')))
 
 
 def skinny_dx_wanted(rows, In, K):
@@ -555,8 +555,8 @@ def skinny_dx_wanted(rows, In, K):
     261 us against 213 us for the 64-row edge tiles -- one 256-row tile per CU streams its 3 MB of dgi AND 3 MB of padded
     weight rows through the same ~25 GB/s per-CU LDS ingest, on 160 of 256 CUs; the edge tiles re-use the weight tile from L1 /
     L2 three blocks per CU.  Same bits either way (tests/test_gpu_gemm_big.py); not the default."""
-    return (os.environ.get('XPS_SKINNY_DX', '0') == '1' and split4_mode() and In % 4 == 0 and In < 256 and rows % 256 == 0
-            and rows >= 96 * 256 and K % 32 == 0 and K >= 512 and os.environ.get('XPS_GEMM_DMA', '1') != '0')
+    return (bool(_switches.get('XPS_SKINNY_DX')) and split4_mode() and In % 4 == 0 and In < 256 and rows % 256 == 0
+            and rows >= 96 * 256 and K % 32 == 0 and K >= 512 and bool(_switches.get('XPS_GEMM_DMA')))
 
 
 def split4_pad(w, ldo):
@@ -591,7 +591,7 @@ class GruPlan(NamedTuple):
 
 
 def gru_layer_plan(T, B, In, H, ndir, drop_p, fmt):
-    """The GruPlan of one layer call under the library state and the environment switches of this moment."""
+    """The GruPlan of one layer call under the library state and the switches (_switches) of this moment."""
     has_drop = bool(drop_p and drop_p > 0.0)
     drop_fused = bool(has_drop and fused_dropout_supported(T, B, H, ndir))
     y_out_split = bool(fmt & FMT_Y_SPLIT4)

@@ -9,11 +9,11 @@ and reference checkpoints work unchanged.  The arithmetic runs in hand-written H
 containers only (identical names, shapes and default initialisation order) and their own
 ``forward`` is never called.
 """
-import os
 
 import torch
 import torch.nn as nn
 
+from .. import _switches
 from . import functional as XF
 from ._lightning import LightningModule
 
@@ -269,7 +269,7 @@ class Seq2SeqRNN(BaseLightningModel):
                                            y if y is not None else None, flags if y is not None else None,
                                            self.num_classes, self.seq_length)
             return logits
-        if rnn.num_layers == 1 and rnn.hidden_size % 4 == 0 and os.environ.get('XPS_DECODER_WIDE', '1') != '0':
+        if rnn.num_layers == 1 and rnn.hidden_size % 4 == 0 and _switches.get('XPS_DECODER_WIDE'):
             # other hidden sizes (H = 500 / 512 of the north-star shape): the same schedule on the general GRU entry points,
             # ONE backward launch per kind for all decode steps (XF.DecoderWideFn)
             table = self.decoder.token_projection()

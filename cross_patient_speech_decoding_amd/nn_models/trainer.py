@@ -19,6 +19,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from .. import _switches
 from . import functional as XF
 
 
@@ -78,7 +79,7 @@ class FlatAdamW:
         # RCCL averages in the collective (no extra pass over the buffer); gloo (CPU tests) sums, then one scale
         self._avg = self._dp and dist.get_backend(group) == 'nccl'
         self._op = dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM
-        if (self._dp and os.environ.get('XPS_DP_OVERLAP', '1') != '0' and XF.DIRECT_GRAD
+        if (self._dp and _switches.get('XPS_DP_OVERLAP') and XF.DIRECT_GRAD
                 and hasattr(module, 'temporal_conv')):
             first = {id(p) for p in module.temporal_conv.parameters()}
             idx = [i for i, p in enumerate(self.params) if id(p) not in first]

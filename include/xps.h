@@ -17,9 +17,9 @@
  *     captured into a hipGraph;
  *   - return value: 0 = ok, negative = error (XPS_E_*); xps_last_error() returns a
  *     thread-local message.  No C++ exception crosses the boundary;
- *   - re-entrant.  Global state: exactly two process-wide mode switches, both plain ints read at call time --
- *     xps_set_gemm_precision (product precision of the matrix kernels) and xps_set_gru_cluster_mode (launch form of the
- *     H > 256 recurrence) -- plus a per-device cache of immutable device facts (CU count, resident workgroups of the cluster kernels) and the
+ *   - re-entrant.  Global state: ONE table of process-wide switches (xps_set_switch below; among them the product precision
+ *     of the matrix kernels and the launch form of the H > 256 recurrence), each a plain integer read at call time,
+ *     plus a per-device cache of immutable device facts (CU count, resident workgroups of the cluster kernels) and the
  *     caller's per-device status word (xps_gru_set_status_word); nothing else outlives a call.
  *
  * Matrices are row-major float32 unless stated.  A "row map" (rpg, gs, ld) addresses
@@ -64,14 +64,23 @@ int xps_abi_version(void);
 /* a HIP stream at the lowest priority of the device (for work that must yield to the caller's main stream) */
 int xps_stream_create_low_priority(void** stream);
 int xps_stream_destroy(void* stream);
+/* The library's switches (README.md, "Switches", lists the rows: name, default, values).  Every row starts at its default or at
+ * what the environment variable of the same name says WHEN THE LIBRARY IS FIRST USED; the environment is not looked at
+ * again, so a change inside a process goes through xps_set_switch (process-wide, not while launches of another thread are
+ * in flight; a workspace is sized and used under the same values).  xps_set_switch: XPS_E_INVALID, with a message, for an
+ * unknown name or a value outside the row's range.  xps_list_switches writes one "NAME=value" line per row into buf (n bytes;
+ * XPS_E_INVALID if they do not fit; 1024 bytes do). */
+int xps_set_switch(const char* name, long long value);
+int xps_get_switch(const char* name, long long* value);
+int xps_list_switches(char* buf, size_t n);
 /* Product precision of the tiled GEMM entry points below (xps_gemm_*) and of the fused GRU recurrence (xps_gru_seq_*,
  * every H): 0 = fp32 MFMA, exact fp32 fma chains; 1 = bf16 split products (the default): every fp32 operand is split hi + lo in bf16 while it is staged and a product is
  * accumulated in fp32 as lo*hi + hi*lo + hi*hi on the bf16 matrix pipe (relative product error ~2^-16; results
- * stay inside the 1e-4 parity bar; BASELINE.json names bf16 for this path).  Process-wide, initial value from
- * XPS_GEMM_PRECISION=fp32|bf16x3; returns XPS_E_INVALID for other modes. */
+ * stay inside the 1e-4 parity bar; BASELINE.json names bf16 for this path).  A view of the row XPS_GEMM_PRECISION
+ * (environment: fp32 | bf16x3); returns XPS_E_INVALID for other modes. */
 int xps_set_gemm_precision(int mode);
 int xps_get_gemm_precision(void);
-/* Tile shape of the matrix kernels in bf16x3 mode: 1 (default; XPS_GEMM_BIG=0 in the environment starts with 0) lets large
+/* Tile shape of the matrix kernels in bf16x3 mode (a view of the row XPS_GEMM_BIG): 1 (default) lets large
  * interior shapes (M, N multiples of 256, k ranges multiples of 16, plain 16-byte aligned operands, >= 192 tiles) run on
  * 256 x 256 tiles / 8 waves; 0 keeps every product on the 128 x 128 (64 x 128) tiles.  Same arithmetic per k-tile in both:
  * products whose k range is not split (nt / nn / nn2 / nt_multi) have the same bits either way. */
@@ -161,7 +170,7 @@ int xps_gru_set_status_word(unsigned* device_word);
 /* BPTT kernel of the cluster path in bf16x3 mode, 384 < H <= 512: 0 (default) = every member of a 16-workgroup cluster contracts
  * all 3H gate-gradient columns of its trials; 1 (XPS_GRU_CL2=1) = the members form a 4 x 4 grid, contract one K slice each and
  * exchange partial sums (a third of the LDS-DMA ingest, a second hand-off per step; same results up to summation order;
- * measured on a par: DESIGN.md 4.5).  Process-wide, read at call time; the workspace query covers both.                       */
+ * measured on a par: DESIGN.md 4.5).  A view of the row XPS_GRU_CL2; the workspace query follows the row.                   */
 int xps_set_gru_bptt_grid(int two_dimensional);
 int xps_get_gru_bptt_grid(void);
 int xps_set_gru_cluster_mode(int mode);

@@ -319,7 +319,7 @@ def test_mcca_fit_is_deterministic():
         np.testing.assert_array_equal(np.asarray(x), np.asarray(y))
 
 
-def test_mcca_cholesky_and_eigendecomposition_whitening_give_the_same_transforms(monkeypatch):
+def test_mcca_cholesky_and_eigendecomposition_whitening_give_the_same_transforms():
     """The two reductions of the pencil (Cholesky factors, default; symmetric R_b^-1/2 by Jacobi, XPS_MCCA_WHITEN=eig) give the same
     eigenvalues and loadings to rounding."""
     from cross_patient_speech_decoding_amd.utils.synthetic import make_patient
@@ -327,9 +327,10 @@ def test_mcca_cholesky_and_eigendecomposition_whitening_give_the_same_transforms
     feats, labs = [p[0] for p in pats], [p[1] for p in pats]
     a = A().AlignMCCA(n_components=10, regs=0.5)
     a.fit(feats, labs)
-    monkeypatch.setenv('XPS_MCCA_WHITEN', 'eig')
+    from cross_patient_speech_decoding_amd import _switches
     b = A().AlignMCCA(n_components=10, regs=0.5)
-    b.fit(feats, labs)
+    with _switches.override(XPS_MCCA_WHITEN='eig'):
+        b.fit(feats, labs)
     np.testing.assert_allclose(a.mcca.evals_, b.mcca.evals_, rtol=1e-11, atol=1e-12)
     for la_, lb_ in zip(a.mcca.loadings_, b.mcca.loadings_):
         np.testing.assert_allclose(la_, lb_, rtol=0, atol=1e-9 * np.abs(lb_).max())

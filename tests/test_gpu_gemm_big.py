@@ -2,6 +2,7 @@
 projections nn_models/models.py:687 (x W_ih^T inside torch.nn.GRU), their input and weight gradients).  The products
 whose k range is not split must equal the 128 x 128-tile kernels BIT FOR BIT (same split arithmetic, same order per
 accumulator); every form is bounded against fp64 by the split-product error model of DESIGN.md 4.0."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -10,7 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from cross_patient_speech_decoding_amd import _build  # noqa: E402
+from cross_patient_speech_decoding_amd import _build, _switches  # noqa: E402
 from cross_patient_speech_decoding_amd._lib import call, lib, rowmap  # noqa: E402
 
 
@@ -23,6 +24,13 @@ def _built():
 def XF():
     from cross_patient_speech_decoding_amd.nn_models import functional
     return functional
+
+
+@pytest.fixture
+def switch():
+    """switch(XPS_NAME=value, ...) sets switches through the one table (_switches.override); all are restored after the test."""
+    with contextlib.ExitStack() as stack:
+        yield lambda **values: stack.enter_context(_switches.override(**values))
 
 
 @pytest.fixture
@@ -173,7 +181,7 @@ def test_weight_gradient_group_mixes_both_tile_shapes(tiles):
                                                    (40960, 1024, 512, 1024, 512, True, True),    # the r, z rows of a dW_hh at full K: B a column window
                                                    (5120, 512, 256, 256, 0, False, False),       # splits with a ragged last chunk
                                                    (4096, 256, 256, 256, 0, True, False)])
-def test_weight_gradient_lds_dma_loop_equals_register_staged_loop_bitwise(K, M, N, ldb, boff, cs, acc, tiles, monkeypatch):
+def test_weight_gradient_lds_dma_loop_equals_register_staged_loop_bitwise(K, M, N, ldb, boff, cs, acc, tiles, switch):
     """The LDS-DMA k loop of the 256-tile weight-gradient kernel (csrc/xps_gemm_dma.h: XPS_FMT_SPLIT4 operands read in place, no
     staging registers / split arithmetic / ds_write) against the register-staged loop (XPS_GEMM_DMA=0) and against the
     128-tile kernels on the SAME split4 operands: products bit for bit (same MFMA order per accumulator), against fp64 within
@@ -197,9 +205,9 @@ def test_weight_gradient_lds_dma_loop_equals_register_staged_loop_bitwise(K, M, 
         return out, db
 
     tiles(1)
-    monkeypatch.setenv('XPS_GEMM_DMA', '1'); dma, dma_cs = run()
+    switch(XPS_GEMM_DMA=1); dma, dma_cs = run()
     again, again_cs = run()
-    monkeypatch.setenv('XPS_GEMM_DMA', '0'); reg, reg_cs = run()
+    switch(XPS_GEMM_DMA=0); reg, reg_cs = run()
     tiles(0); small, small_cs = run()
     assert torch.equal(dma, reg) and torch.equal(dma, again)
     a64, b64 = A.double(), Bfull.double()[:, boff:boff + N]
@@ -215,7 +223,7 @@ def test_weight_gradient_lds_dma_loop_equals_register_staged_loop_bitwise(K, M, 
 
 
 @pytest.mark.parametrize('K', [32, 96, 1024])
-def test_direct_forms_lds_dma_loop_equals_register_staged_loop_bitwise(K, tiles, monkeypatch):
+def test_direct_forms_lds_dma_loop_equals_register_staged_loop_bitwise(K, tiles, switch):
     """The LDS-DMA k loop of the direct 256-tile forms (csrc/xps_gemm_dma.h: direct_dma_pipeline; XPS_FMT_SPLIT4 operands, [x][k]
     rows moved as whole cache lines with a source-side bank swizzle, group pairs regrouped in registers; the [k][x] operand of
     the NN form through transposing reads) against the register-staged loop (XPS_GEMM_DMA=0) and the 128-tile kernels: NT, NN,
@@ -248,8 +256,8 @@ def test_direct_forms_lds_dma_loop_equals_register_staged_loop_bitwise(K, tiles,
         return c_nt, c_nn, c_nn2, cs[0], cs[1]
 
     tiles(1)
-    monkeypatch.setenv('XPS_GEMM_DMA', '1'); dma = run()
-    monkeypatch.setenv('XPS_GEMM_DMA', '0'); reg = run()
+    switch(XPS_GEMM_DMA=1); dma = run()
+    switch(XPS_GEMM_DMA=0); reg = run()
     tiles(0); small = run()
     for a, b, c in zip(dma, reg, small):
         assert torch.equal(a, b) and torch.equal(a, c)
@@ -261,7 +269,7 @@ def test_direct_forms_lds_dma_loop_equals_register_staged_loop_bitwise(K, tiles,
 
 
 @pytest.mark.parametrize('N', [100, 64, 200])
-def test_skinny_input_gradient_on_the_lds_dma_loop_equals_edge_tiles_bitwise(N, tiles, monkeypatch):
+def test_skinny_input_gradient_on_the_lds_dma_loop_equals_edge_tiles_bitwise(N, tiles, switch):
     """configs[3] layer 0: dx = dgi_fwd W_fwd + dgi_bwd W_bwd with In = 100 input channels (40960 x 100 x 2 * 1536; here 24576 rows).
     The product is bound by the read of dgi: with W handed over as a zero-padded 256-column split4 image (xps_split4_pad_f32) it
     runs ONE 256-wide tile per 256 rows on the LDS-DMA loop (gemm_big_kernel<.., 5>: waves beyond column N idle, masked C
@@ -284,7 +292,7 @@ def test_skinny_input_gradient_on_the_lds_dma_loop_equals_edge_tiles_bitwise(N, 
         return out
 
     tiles(1)
-    monkeypatch.setenv('XPS_GEMM_DMA', '1')
+    switch(XPS_GEMM_DMA=1)
     P1, P2 = xf.split4_pad(W1, 256), xf.split4_pad(W2, 256)
     assert P1.shape == (K, 256) and float(P1[:, N:].abs().max()) == 0.0
     dma = nn2(P1, P2, rowmap(256, fmt=1))
@@ -293,13 +301,13 @@ def test_skinny_input_gradient_on_the_lds_dma_loop_equals_edge_tiles_bitwise(N, 
     assert torch.equal(dma, edge) and torch.equal(dma, plain)
     ref = A1.double() @ W1.double() + A2.double() @ W2.double()
     assert bool(((dma.double() - ref).abs() <= _bound(A1.double(), W1.double()) + _bound(A2.double(), W2.double()) + 1e-5).all())
-    monkeypatch.setenv('XPS_SKINNY_DX', '1')                                   # (opt-in: measured slower than the edge tiles)
+    switch(XPS_SKINNY_DX=1)                                                    # (opt-in: measured slower than the edge tiles)
     assert xf.skinny_dx_wanted(40960, 100, 1536) and not xf.skinny_dx_wanted(40960, 1024, 1536)
 
 
 def test_opt_in_32_deep_stages_same_bits():
-    """XPS_GEMM_BIG_DEEP=1 (32-deep LDS stages with swizzled [x][k] images, read once per process): the direct forms must
-    still equal the 128-tile kernels bit for bit.  Own process because the switch is read at first use."""
+    """XPS_GEMM_BIG_DEEP=1 (32-deep LDS stages with swizzled [x][k] images) in the environment of a fresh process -- the
+    start-of-process route into the switch table: the direct forms must still equal the 128-tile kernels bit for bit."""
     import os
     import subprocess
     import sys

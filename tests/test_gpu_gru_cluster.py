@@ -3,13 +3,15 @@ north-star shape H = 512 and the reference default H = 500, nn_models/models.py:
 against torch.nn.GRU on the CPU (what the reference calls), and the three launch modes against each other --
 'persistent' (in-kernel hand-off between the workgroups of a cluster) must equal 'steps' (the same kernels, one
 launch per step: the kernel boundary is the hand-off) BIT FOR BIT, at full bench size, repeatedly."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from cross_patient_speech_decoding_amd import _build  # noqa: E402
+from cross_patient_speech_decoding_amd import _build, _switches  # noqa: E402
 from cross_patient_speech_decoding_amd._lib import lib  # noqa: E402
 
 
@@ -22,6 +24,13 @@ def _built():
 def XF():
     from cross_patient_speech_decoding_amd.nn_models import functional
     return functional
+
+
+@pytest.fixture
+def switch():
+    """switch(XPS_NAME=value, ...) sets switches through the one table (_switches.override); all are restored after the test."""
+    with contextlib.ExitStack() as stack:
+        yield lambda **values: stack.enter_context(_switches.override(**values))
 
 
 @pytest.fixture
@@ -226,7 +235,7 @@ def test_persistent_under_concurrent_load(cluster_mode):
 
 @pytest.mark.parametrize('mode', ['persistent', 'steps'])
 @pytest.mark.parametrize('T,B,ndir,need_dh0', [(4, 512, 2, False), (3, 256, 1, True), (1, 2048, 2, True)])
-def test_bptt_with_outputs_as_exchange_rows_equals_the_ring_bitwise(T, B, ndir, need_dh0, mode, cluster_mode, monkeypatch):
+def test_bptt_with_outputs_as_exchange_rows_equals_the_ring_bitwise(T, B, ndir, need_dh0, mode, cluster_mode, switch):
     """XPS_GRU_XOUT=1 (gru_cluster_bwd_kernel<.., XOUT>: the operand images of step ps are moved from the dgi / dghn rows step ps - 1
     wrote, no exchange ring; H = 512, bf16x3, split4 outputs) gives the bits of the default kernel: dgi, dghn, dh0."""
     xf = XF()
@@ -242,8 +251,8 @@ def test_bptt_with_outputs_as_exchange_rows_equals_the_ring_bitwise(T, B, ndir, 
         dy, dhn = (torch.randn(T, B, ndir * H, generator=g) * 0.1).cuda(), (torch.randn(ndir, B, H, generator=g) * 0.1).cuda()
         y_ext, saved = xf._gru_forward(gi, w_hh, b_hh, None, T, B, H, ndir, True)
         outs = []
-        for flag in ('0', '1'):
-            monkeypatch.setenv('XPS_GRU_XOUT', flag)
+        for flag in (0, 1):
+            switch(XPS_GRU_XOUT=flag)
             outs.append(xf._gru_backward(dy, dhn, y_ext, saved, w_hh, T, B, H, ndir, need_dh0, split4=True))
         torch.cuda.synchronize()
         xf.check_gru_status()
@@ -275,7 +284,7 @@ def test_launch_form_change_between_forward_and_backward_is_refused(cluster_mode
     xf.check_gru_status()
 
 
-def test_backward_follows_the_plan_of_its_forward_when_switches_flip_in_between(gemm_precision, monkeypatch):
+def test_backward_follows_the_plan_of_its_forward_when_switches_flip_in_between(gemm_precision, switch):
     """GRULayerFmtFn.forward decides the operand formats of both passes once (functional.gru_layer_plan) and the backward obeys
     that plan: a two-layer encoder in training mode whose XPS_SPLIT4 / XPS_HPREV_SPLIT / XPS_FWD_YSPLIT switches go to 0 between
     forward and backward (memo dropped, so every predicate WOULD answer anew) gives the bits of the run without the flip --
@@ -299,21 +308,15 @@ def test_backward_follows_the_plan_of_its_forward_when_switches_flip_in_between(
         loss = (y * wy).sum() + (last * wl).sum()
         if flip:
             before = xf.hprev_split_wanted(T, B, H, 2)            # (implies split4_wanted)
-            for k in switches:
-                monkeypatch.setenv(k, '0')
-            xf._memo.clear()
+            switch(**{k: 0 for k in switches})
             assert before == (gemm_precision == 'bf16x3') and not xf.split4_wanted(T, B, H, 2)
         loss.backward()
         torch.cuda.synchronize()
         xf.check_gru_status()
         return [y.detach().clone(), last.detach().clone(), xg.grad.clone()] + [p.grad.clone() for p in enc.parameters()]
 
-    try:
-        base = run(False)
-        flipped = run(True)
-    finally:
-        monkeypatch.undo()
-        xf._memo.clear()
+    base = run(False)
+    flipped = run(True)
     assert len(base) == len(flipped) == 3 + 16
     for a, b in zip(base, flipped):
         assert torch.equal(a, b)

@@ -3,6 +3,7 @@ GEMMs read writes it ONCE (16-byte groups hi[0..3] | lo[0..3]); the tile kernels
 The contract tested here: products are BIT-IDENTICAL to those from the fp32 operand (every GEMM form, small and 256-tile
 kernels), a bias gradient folded from a split4 operand is within 2^-17 relative per element of the fp32 one, the BPTT kernels'
 split4 outputs are exactly split4(fp32 outputs), and requests that cannot be served fail loudly."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -11,7 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from cross_patient_speech_decoding_amd import _build  # noqa: E402
+from cross_patient_speech_decoding_amd import _build, _switches  # noqa: E402
 from cross_patient_speech_decoding_amd._lib import XpsError, call, lib, rowmap  # noqa: E402
 
 
@@ -27,6 +28,13 @@ def _bf16x3():
     assert lib().xps_set_gemm_precision(1) == 0
     yield
     lib().xps_set_gemm_precision(old)
+
+
+@pytest.fixture
+def switch():
+    """switch(XPS_NAME=value, ...) sets switches through the one table (_switches.override); all are restored after the test."""
+    with contextlib.ExitStack() as stack:
+        yield lambda **values: stack.enter_context(_switches.override(**values))
 
 
 def XF():
@@ -234,7 +242,7 @@ def test_forward_images_are_refused_off_the_cluster_path():
         F._gru_forward_images(gi, [rnd(384, 128)], [rnd(384)], 2, 64, 128, 1, True, False, None)
 
 
-def test_layer_with_forward_kernel_images_equals_the_split_passes(monkeypatch):
+def test_layer_with_forward_kernel_images_equals_the_split_passes(switch):
     """Two-layer bidirectional encoder, training mode: XPS_FWD_IMAGES=1 (images from the recurrence kernel) against =0 (one
     xps_split4_f32 pass per image): outputs and every gradient bit-identical."""
     from cross_patient_speech_decoding_amd.nn_models.models import EncoderRNN
@@ -248,7 +256,7 @@ def test_layer_with_forward_kernel_images_equals_the_split_passes(monkeypatch):
     wy, wl = rnd(T, B, 2 * H, seed=6), rnd(B, H, seed=7)
 
     def run(flag):
-        monkeypatch.setenv('XPS_FWD_IMAGES', flag)
+        switch(XPS_FWD_IMAGES=int(flag))
         assert F.fwd_images_wanted(T, B, H, 2) == (flag == '1')
         F._DROP_COUNTER[0] = 4321
         enc.zero_grad(set_to_none=True)
@@ -262,14 +270,14 @@ def test_layer_with_forward_kernel_images_equals_the_split_passes(monkeypatch):
     base = run('0')                                      # (default: y_ext's image is the forward launch's exchange buffer)
     for a, b in zip(base, run('1')):
         assert torch.equal(a, b)
-    monkeypatch.setenv('XPS_FWD_YSPLIT', '0')            # ring-buffer exchange + one xps_split4_f32 pass per image
+    switch(XPS_FWD_YSPLIT=0)                             # ring-buffer exchange + one xps_split4_f32 pass per image
     assert not F.fwd_ysplit_wanted(T, B, H, 2)
     for a, b in zip(base, run('0')):
         assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize('H,In', [(512, 100), (500, 32), (128, 64)])
-def test_encoder_stack_with_split4_tensors_equals_the_fp32_tensor_path(H, In, monkeypatch):
+def test_encoder_stack_with_split4_tensors_equals_the_fp32_tensor_path(H, In, switch):
     """Two-layer bidirectional encoder in TRAINING mode (inter-layer dropout on), XPS_SPLIT4=1 (dgi / dghn, the dropped
     layer output and the large W_ih travel as XPS_FMT_SPLIT4 operands) against XPS_SPLIT4=0 (fp32 tensors everywhere), same
     dropout seeds: outputs, input gradient and every weight gradient BIT-IDENTICAL; bias gradients (column sums of a split4
@@ -283,8 +291,7 @@ def test_encoder_stack_with_split4_tensors_equals_the_fp32_tensor_path(H, In, mo
     wy, wl = rnd(T, B, 2 * H, seed=6), rnd(B, H, seed=7)
 
     def run(flag):
-        monkeypatch.setenv('XPS_SPLIT4', flag)
-        F._memo.clear()
+        switch(XPS_SPLIT4=int(flag))
         F._DROP_COUNTER[0] = 12345
         enc.zero_grad(set_to_none=True)
         xg = x.clone().requires_grad_(True)
@@ -296,7 +303,6 @@ def test_encoder_stack_with_split4_tensors_equals_the_fp32_tensor_path(H, In, mo
 
     y0, l0, dx0, g0 = run('0')
     y1, l1, dx1, g1 = run('1')
-    F._memo.clear()
     assert torch.equal(y1, y0) and torch.equal(l1, l0) and torch.equal(dx1, dx0)
     for k in g0:
         if 'bias' in k:
@@ -311,7 +317,7 @@ def test_encoder_stack_with_split4_tensors_equals_the_fp32_tensor_path(H, In, mo
 
 @pytest.mark.parametrize('M,N,K,nprob', [(40960, 384, 256, 2), (40960, 384, 100, 2), (4100, 96, 64, 3), (8192, 256, 32, 1),
                                          (5000, 160, 200, 2)])
-def test_weight_stationary_projection_equals_the_tile_kernels_bitwise(M, N, K, nprob, monkeypatch):
+def test_weight_stationary_projection_equals_the_tile_kernels_bitwise(M, N, K, nprob, switch):
     """proj_ws_kernel (weights of a 256-column slice resident in registers, A streamed once per slice; csrc/xps_gemm.hip) issues
     the same products in the same order per accumulator as the tile kernels: identical bits, for fp32 and XPS_FMT_SPLIT4
     operands, ragged row counts, K that is not a multiple of 32, column slices that straddle problems or are partly idle."""
@@ -328,9 +334,9 @@ def test_weight_stationary_projection_equals_the_tile_kernels_bitwise(M, N, K, n
         torch.cuda.synchronize()
         return outs
 
-    monkeypatch.setenv('XPS_PROJ_WS', '0')
+    switch(XPS_PROJ_WS=0)
     ref = run(A, W, 0, 0)
-    monkeypatch.setenv('XPS_PROJ_WS', '1')
+    switch(XPS_PROJ_WS=1)
     for fa, fb in [(0, 0), (1, 0), (1, 1)]:
         got = run(split4(A) if fa else A, [split4(w) for w in W] if fb else W, fa, fb)
         for i in range(nprob):

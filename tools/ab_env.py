@@ -1,5 +1,5 @@
 """Interleaved A/B of the headline step under environment switches: python tools/ab_env.py VAR=a,b [VAR2=c,d ...] [--steps N] [--rounds R]
-Every combination is run `rounds` times in turn (own process each: the switches are read at first use), ms/step printed per run."""
+Every combination is run `rounds` times in turn (own process each: the switch tables start from the environment of their process), ms/step printed per run."""
 import itertools, json, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 steps, rounds, sw = 40, 2, []

@@ -2,6 +2,7 @@
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from cross_patient_speech_decoding_amd import _switches
 from cross_patient_speech_decoding_amd._lib import call, rowmap
 from cross_patient_speech_decoding_amd.nn_models import functional as F
 
@@ -23,8 +24,8 @@ for M, N, K, nprob in [(40960, 384, 256, 2), (40960, 384, 100, 2), (40960, 192, 
     fn = lambda: call('xps_gemm_nt_multi_f32', A.data_ptr(), C.byref(ra), F._ptr_array(W), C.byref(rb), F._ptr_array(outs), C.byref(rc),
                       F._ptr_array(bs), nprob, M, N, K, F._stream())
     res = []
-    for v in ('0', '1', '0', '1'):
-        os.environ['XPS_PROJ_WS'] = v
-        res.append('%s: %6.1f us' % (v, timeit(fn)))
+    for v in (0, 1, 0, 1):
+        with _switches.override(XPS_PROJ_WS=v):
+            res.append('%d: %6.1f us' % (v, timeit(fn)))
     mb = (M * K + nprob * M * N) * 4 / 1e6
     print(f'M={M} N={N} K={K} x{nprob}  ({mb:.0f} MB)  ' + '  '.join(res))

@@ -5,6 +5,7 @@ XPS_HPREV_SPLIT=1: h_prev handed over as an XPS_FMT_SPLIT4 copy too (what a spli
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from cross_patient_speech_decoding_amd import _switches
 from cross_patient_speech_decoding_amd._lib import rowmap
 from cross_patient_speech_decoding_amd.nn_models import functional as XF
 
@@ -52,8 +53,8 @@ for which in (None, 'dW_ih', 'dW_hh rz', 'dW_hh n'):
     res = []
     for rnd in range(2):
         for dma in ('0', '1'):
-            os.environ['XPS_GEMM_DMA'] = dma
-            res.append((dma, timeit(lambda: XF.gemm_tn_grouped(pr, dev))))
+            with _switches.override(XPS_GEMM_DMA=int(dma)):
+                res.append((dma, timeit(lambda: XF.gemm_tn_grouped(pr, dev))))
     s = ', '.join(f'DMA={d}: {t:7.1f} us' for d, t in res)
     best = min(t for d, t in res if d == '1')
     print(f'{which or "whole group (6 problems)":26s} {s}   [{3 * flop / best / 1e6 / 2500e0:.3f} of the bf16 peak issued with DMA]', flush=True)

@@ -1,6 +1,6 @@
 // Prototype harness for csrc/xps_gemm_dma.h: the LDS-DMA k loop of the 256-tile weight-gradient GEMM against the
 // register-staged loop of xps_gemm_big.h on the same split4 operands (bits + time), stand-alone (no torch, no libxps).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DXPS_DMA_SHIFT8=0] -o tn_dma tools/proto/tn_dma.hip && ./tn_dma [M N K splits]
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tn_dma tools/proto/tn_dma.hip && ./tn_dma [M N K splits]
 #include "../../cross_patient_speech_decoding_amd/csrc/xps_gemm_dma.h"
 #include <cmath>
 #include <cstdlib>
@@ -89,7 +89,7 @@ int main(int argc, char** argv) {
     const int M = argc > 1 ? atoi(argv[1]) : 1536, N = argc > 2 ? atoi(argv[2]) : 1024, K = argc > 3 ? atoi(argv[3]) : 40960;
     const int splits = argc > 4 ? atoi(argv[4]) : 10;
     if (M % 256 || N % 256 || K % (16 * splits)) { printf("bad shape\n"); return 1; }
-    printf("TN %d x %d x %d, %d k-splits (%d blocks), DMA row shift8 = %d, LDS %d B\n", M, N, K, splits, (M / 256) * (N / 256) * splits, XPS_DMA_SHIFT8, DMA_LDS);
+    printf("TN %d x %d x %d, %d k-splits (%d blocks), LDS %d B\n", M, N, K, splits, (M / 256) * (N / 256) * splits, DMA_LDS);
     std::vector<float> hA((size_t)K * M), hB((size_t)K * N);
     srand(7);
     for (auto& x : hA) x = randn();

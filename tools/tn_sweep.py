@@ -1,4 +1,4 @@
-"""TN (weight-gradient) GEMM: time vs number of blocks (XPS_TN_BLOCKS is read once per process)."""
+"""TN (weight-gradient) GEMM: time vs number of blocks (one process per XPS_TN_BLOCKS value: the environment is read when the library is first used)."""
 import os, subprocess, sys
 here = os.path.dirname(os.path.abspath(__file__))
 if len(sys.argv) > 1 and sys.argv[1] == 'child':
