@@ -394,8 +394,10 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(GruBwdParams p) {
 // Operand roles are SWAPPED relative to the streaming kernel: A = W_hh fragment (row = hidden
 // unit), B = h^T (col = trial), so D[row = unit 4*kq + i][col = trial n]: every lane owns FOUR
 // CONSECUTIVE hidden units of ONE trial, and all per-step traffic (gi in, h out, saved gates,
-// LDS state) is 16-byte vectors.  Activations use v_exp_f32 / v_rcp_f32 (abs error ~1e-7,
-// far inside the 1e-4 logit budget).
+// LDS state) is 16-byte vectors.  Activations use v_exp_f32 / v_rcp_f32 (both 1 ulp): abs error
+// <= 3 u for the sigmoid and 6.5 u for the tanh, u = 2^-24 (derivation: tests/gru_seq_ref.py, held
+// on the device by tests/test_gpu_gru_recurrence.py), far inside the 1e-4 logit budget; an exponential
+// that overflows gives rcp(inf) = 0, i.e. exactly 0 / -1, never NaN.
 // ---------------------------------------------------------------------------------------------
 __device__ inline float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ inline float fast_tanh(float x) { return 2.0f * fast_sigmoid(2.0f * x) - 1.0f; }
@@ -1223,6 +1225,35 @@ extern "C" long long xps_gru_seq_status_offset(int T, int B, int H, int ndir) {
     return cluster_shape_ok(T, B, H, ndir) ? (long long)xps_internal_gru_cluster_status_offset(B, H, ndir) : -1;
 }
 
+// The ONE dispatch decision of the recurrence entry points (xps.h: XPS_GRU_ROUTE_*); gru_seq_fwd_impl and gru_seq_bwd_impl
+// launch what it returns and xps_gru_seq_route reports it.  whh_aligned / whht_aligned: every W_hh / W_hh^T pointer of the call
+// is 16-byte aligned.  The forward streams W_hh on every route; the backward streams W_hh^T on the LDS-tile routes (H <= 128,
+// or XPS_GRU_STEP_PATH=0) and W_hh on the per-step route, so the pointer that decides `vec` differs by route.
+// The LDS-tile kernels keep 16 trials x (3 Hp + 4 + Hp + 4) floats (backward; the forward's 2 x 16 x (Hp + 4) is smaller) in at
+// most 160 KiB: Hp <= 624.  Both directions stop there, so that no forward writes `saved` for a backward that is refused.
+constexpr int GRU_MAX_H_TILE = XPS_GRU_MAX_H_TILE;
+constexpr int GRU_MAX_H_STEP = XPS_GRU_MAX_H_STEP;
+static_assert((size_t)GBM * (4 * (((GRU_MAX_H_TILE + 15) / 16) * 16) + 8) * sizeof(float) <= 160 * 1024 &&
+              (size_t)GBM * (4 * (((GRU_MAX_H_TILE + 16) / 16) * 16) + 8) * sizeof(float) > 160 * 1024,
+              "XPS_GRU_MAX_H_TILE is the largest H whose gradient tile fits 160 KiB of LDS");
+static int gru_route(int T, int B, int H, int ndir, bool whh_aligned, bool whht_aligned, bool backward) {
+    if (T < 1 || B < 1 || H < 1 || (ndir != 1 && ndir != 2)) return XPS_GRU_ROUTE_REFUSED;
+    if (cluster_shape_ok(T, B, H, ndir)) return XPS_GRU_ROUTE_CLUSTER;
+    if (H > 128 && use_step_path()) {
+        if (H > GRU_MAX_H_STEP) return XPS_GRU_ROUTE_REFUSED;
+        const int v4 = (H % 4 == 0) ? 1 : 0;
+        return XPS_GRU_ROUTE_STEP | (v4 ? XPS_GRU_ROUTE_STEP_VECA : 0) | ((v4 && whh_aligned) ? XPS_GRU_ROUTE_STEP_VECB : 0);
+    }
+    if (H > GRU_MAX_H_TILE) return XPS_GRU_ROUTE_REFUSED;
+    const bool vec = (H % 4 == 0) && (backward ? whht_aligned : whh_aligned);
+    if (vec && (H == 128 || H == 64)) return XPS_GRU_ROUTE_RESIDENT;
+    return vec ? XPS_GRU_ROUTE_GENERIC_VEC : XPS_GRU_ROUTE_GENERIC_SCALAR;
+}
+
+extern "C" int xps_gru_seq_route(int T, int B, int H, int ndir, int weights_aligned16, int backward) {
+    return gru_route(T, B, H, ndir, weights_aligned16 != 0, weights_aligned16 != 0, backward != 0);
+}
+
 // the shapes whose forward / backward run the register-resident kernels (the only ones that fuse the inter-layer dropout)
 extern "C" int xps_gru_seq_fused_dropout_supported(int T, int B, int H, int ndir) {
     if (T < 1 || B < 1 || (ndir != 1 && ndir != 2)) return 0;
@@ -1288,8 +1319,11 @@ static int gru_seq_fwd_impl(const float* gi, const float* const* w_hh, const flo
     XPS_CHECK_ARG(gi && w_hh && b_hh && y_ext, "null argument");
     XPS_CHECK_ARG(T >= 1 && B >= 1 && H >= 1, "T, B, H must be >= 1");
     XPS_CHECK_ARG(ndir == 1 || ndir == 2, "ndir must be 1 or 2");
-    if (cluster_shape_ok(T, B, H, ndir)) {
-        XPS_CHECK_ARG(w_hh[0] && b_hh[0] && (ndir == 1 || (w_hh[1] && b_hh[1])), "null weight pointer");
+    XPS_CHECK_ARG(w_hh[0] && b_hh[0] && (ndir == 1 || (w_hh[1] && b_hh[1])), "null weight pointer");
+    const bool w_aligned = aligned16(w_hh[0]) && (ndir == 1 || aligned16(w_hh[1]));
+    const int route = gru_route(T, B, H, ndir, w_aligned, w_aligned, false);
+    XPS_CHECK_ARG(route != XPS_GRU_ROUTE_REFUSED, "hidden size beyond the route's limit (xps.h: XPS_GRU_MAX_H_TILE / XPS_GRU_MAX_H_STEP)");
+    if (route == XPS_GRU_ROUTE_CLUSTER) {
         if (!workspace || workspace_bytes < xps_gru_seq_fwd_f32_workspace(T, B, H, ndir)) {
             xps_set_error("xps_gru_seq_fwd_f32: workspace too small");
             return XPS_E_WORKSPACE;
@@ -1303,17 +1337,13 @@ static int gru_seq_fwd_impl(const float* gi, const float* const* w_hh, const flo
     p.y_drop = y_drop; p.drop_p = drop_p; p.drop_scale = 1.0f / (1.0f - drop_p); p.drop_seed = drop_seed;
     p.Hp = ((H + 15) / 16) * 16;
     p.ldh = p.Hp + 4;
-    bool vec = (H % 4 == 0);
     for (int d = 0; d < 2; ++d) {
         p.w_hh[d] = w_hh[d < ndir ? d : 0];
         p.b_hh[d] = b_hh[d < ndir ? d : 0];
-        XPS_CHECK_ARG(p.w_hh[d] && p.b_hh[d], "null weight pointer");
-        vec = vec && aligned16(p.w_hh[d]);
     }
-    const size_t lds_bytes = (size_t)2 * GBM * p.ldh * sizeof(float);
-    XPS_CHECK_ARG(lds_bytes <= 160 * 1024, "hidden size too large for the LDS-resident state tile");
+    const bool vec = (H % 4 == 0) && w_aligned;
     XPS_CHECK_ARG(!y_drop || vec, "fused dropout needs 16-byte aligned weights");
-    if (H > 128 && use_step_path()) {
+    if (route & XPS_GRU_ROUTE_STEP) {
         // large hidden size: one fused GEMM + gate launch per time step (see gru_step_fwd_kernel)
         hipStream_t st = (hipStream_t)stream;
         hipLaunchKernelGGL(gru_init_slots_kernel, dim3(cdiv((long long)ndir * B * H, 256) > 1024 ? 1024 : cdiv((long long)ndir * B * H, 256)),
@@ -1321,8 +1351,8 @@ static int gru_seq_fwd_impl(const float* gi, const float* const* w_hh, const flo
         GruStepFwd q;
         q.gi = gi; q.y_ext = y_ext; q.saved = saved; q.T = T; q.B = B; q.H = H; q.ndir = ndir;
         for (int d = 0; d < 2; ++d) { q.w_hh[d] = p.w_hh[d]; q.b_hh[d] = p.b_hh[d]; }
-        q.vecA = (int)(H % 4 == 0 && aligned16(y_ext));
-        q.vecB = (int)vec;
+        q.vecA = (int)((route & XPS_GRU_ROUTE_STEP_VECA) && aligned16(y_ext));
+        q.vecB = (route & XPS_GRU_ROUTE_STEP_VECB) ? 1 : 0;
         dim3 sgrid(cdiv(H, 32), cdiv(B, 128), ndir);
         for (int s = 0; s < T; ++s) {
             q.s = s;
@@ -1333,7 +1363,7 @@ static int gru_seq_fwd_impl(const float* gi, const float* const* w_hh, const flo
         return XPS_OK;
     }
     dim3 grid(cdiv(B, GBM), ndir);
-    if (vec && (H == 128 || H == 64)) {
+    if (route == XPS_GRU_ROUTE_RESIDENT) {
         const bool bf = xps_internal_gemm_mode() == 1;
         if (H == 128 && bf) hipLaunchKernelGGL((gru_fwd_resident_kernel<128, true, GRU_BF_WAVES>), grid, dim3(GRU_BF_WAVES * 64), 0, (hipStream_t)stream, p);
         else if (H == 128) hipLaunchKernelGGL((gru_fwd_resident_kernel<128, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
@@ -1342,7 +1372,8 @@ static int gru_seq_fwd_impl(const float* gi, const float* const* w_hh, const flo
         XPS_CHECK_LAUNCH();
         return XPS_OK;
     }
-    if (vec) {
+    const size_t lds_bytes = (size_t)2 * GBM * p.ldh * sizeof(float);        // <= 160 KiB: H <= XPS_GRU_MAX_H_TILE on these routes
+    if (route == XPS_GRU_ROUTE_GENERIC_VEC) {
         if (lds_bytes > 64 * 1024)
             if (hipFuncSetAttribute((const void*)gru_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) { xps_set_error("hipFuncSetAttribute failed"); return XPS_E_HIP; }
         hipLaunchKernelGGL(gru_fwd_kernel<true>, grid, dim3(256), lds_bytes, (hipStream_t)stream, p);
@@ -1411,8 +1442,13 @@ static int gru_seq_bwd_impl(const float* dy, const float* dhn, const float* y_ex
     XPS_CHECK_ARG(dy || dhn, "at least one of dy / dhn must be given");
     XPS_CHECK_ARG(T >= 1 && B >= 1 && H >= 1, "T, B, H must be >= 1");
     XPS_CHECK_ARG(ndir == 1 || ndir == 2, "ndir must be 1 or 2");
-    if (cluster_shape_ok(T, B, H, ndir)) {
-        XPS_CHECK_ARG(w_hh_t[0] && (ndir == 1 || w_hh_t[1]), "null weight pointer");
+    XPS_CHECK_ARG(w_hh_t[0] && (ndir == 1 || w_hh_t[1]), "null weight pointer");
+    // (W_hh itself is read by the per-step route only: the other routes accept NULL entries, as they always have)
+    const bool whh_aligned = aligned16(w_hh[0]) && (ndir == 1 || aligned16(w_hh[1]));
+    const bool whht_aligned = aligned16(w_hh_t[0]) && (ndir == 1 || aligned16(w_hh_t[1]));
+    const int route = gru_route(T, B, H, ndir, whh_aligned, whht_aligned, true);
+    XPS_CHECK_ARG(route != XPS_GRU_ROUTE_REFUSED, "hidden size beyond the route's limit (xps.h: XPS_GRU_MAX_H_TILE / XPS_GRU_MAX_H_STEP)");
+    if (route == XPS_GRU_ROUTE_CLUSTER) {
         if (!workspace || workspace_bytes < xps_gru_seq_bwd_f32_workspace(T, B, H, ndir)) {
             xps_set_error("xps_gru_seq_bwd_f32: workspace too small");
             return XPS_E_WORKSPACE;
@@ -1427,17 +1463,11 @@ static int gru_seq_bwd_impl(const float* dy, const float* dhn, const float* y_ex
     p.Hp = ((H + 15) / 16) * 16;
     p.ldg = 3 * p.Hp + 4;
     p.ldc = p.Hp + 4;
-    bool vec = (H % 4 == 0);
-    for (int d = 0; d < 2; ++d) {
-        p.w_hh_t[d] = w_hh_t[d < ndir ? d : 0];
-        XPS_CHECK_ARG(p.w_hh_t[d], "null weight pointer");
-        vec = vec && aligned16(p.w_hh_t[d]);
-    }
-    const size_t lds_bytes = (size_t)GBM * (p.ldg + p.ldc) * sizeof(float);
-    XPS_CHECK_ARG(lds_bytes <= 160 * 1024, "hidden size too large for the LDS-resident gradient tile");
+    for (int d = 0; d < 2; ++d) p.w_hh_t[d] = w_hh_t[d < ndir ? d : 0];
+    const bool vec = (H % 4 == 0) && whht_aligned;
     XPS_CHECK_ARG(!has_drop || vec, "fused dropout needs 16-byte aligned weights");
     XPS_CHECK_ARG(!split_out || (vec && (H == 128 || H == 64)), "XPS_FMT_SPLIT4 outputs need the resident kernels (16-byte aligned weights)");
-    if (H > 128 && use_step_path()) {
+    if (route & XPS_GRU_ROUTE_STEP) {
         if (!workspace || workspace_bytes < xps_gru_seq_bwd_f32_workspace(T, B, H, ndir) || !aligned16(workspace)) {
             xps_set_error("xps_gru_seq_bwd_f32: workspace too small or misaligned");
             return XPS_E_WORKSPACE;
@@ -1446,15 +1476,13 @@ static int gru_seq_bwd_impl(const float* dy, const float* dhn, const float* y_ex
         GruStepBwd q;
         q.dy = dy; q.dhn = dhn; q.y_ext = y_ext; q.saved = saved; q.dgi = dgi; q.dghn = dghn; q.dh0 = dh0;
         q.T = T; q.B = B; q.H = H; q.ndir = ndir;
-        bool vb = (H % 4 == 0);
         for (int d = 0; d < 2; ++d) {
             q.w_hh[d] = w_hh[d < ndir ? d : 0];
             XPS_CHECK_ARG(q.w_hh[d], "null weight pointer");
-            vb = vb && aligned16(q.w_hh[d]);
         }
-        q.vecB = (int)vb;
-        q.vecA1 = (int)(H % 4 == 0 && aligned16(dgi));
-        q.vecA2 = (int)(H % 4 == 0 && aligned16(dghn));
+        q.vecB = (route & XPS_GRU_ROUTE_STEP_VECB) ? 1 : 0;
+        q.vecA1 = (int)((route & XPS_GRU_ROUTE_STEP_VECA) && aligned16(dgi));
+        q.vecA2 = (int)((route & XPS_GRU_ROUTE_STEP_VECA) && aligned16(dghn));
         float* keep[2] = {(float*)workspace, (float*)workspace + (size_t)ndir * B * H};
         dim3 sgrid(cdiv(H, 128), cdiv(B, 64), ndir);
         int pp = 0;
@@ -1474,7 +1502,7 @@ static int gru_seq_bwd_impl(const float* dy, const float* dhn, const float* y_ex
         return XPS_OK;
     }
     dim3 grid(cdiv(B, GBM), ndir);
-    if (vec && (H == 128 || H == 64)) {
+    if (route == XPS_GRU_ROUTE_RESIDENT) {
         const bool bf = xps_internal_gemm_mode() == 1;
         if (H == 128 && bf) hipLaunchKernelGGL((gru_bwd_resident_kernel<128, true, GRU_BF_WAVES>), grid, dim3(GRU_BF_WAVES * 64), 0, (hipStream_t)stream, p);
         else if (H == 128) hipLaunchKernelGGL((gru_bwd_resident_kernel<128, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
@@ -1483,7 +1511,8 @@ static int gru_seq_bwd_impl(const float* dy, const float* dhn, const float* y_ex
         XPS_CHECK_LAUNCH();
         return XPS_OK;
     }
-    if (vec) {
+    const size_t lds_bytes = (size_t)GBM * (p.ldg + p.ldc) * sizeof(float);  // <= 160 KiB: H <= XPS_GRU_MAX_H_TILE on these routes
+    if (route == XPS_GRU_ROUTE_GENERIC_VEC) {
         if (lds_bytes > 64 * 1024)
             if (hipFuncSetAttribute((const void*)gru_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) { xps_set_error("hipFuncSetAttribute failed"); return XPS_E_HIP; }
         hipLaunchKernelGGL(gru_bwd_kernel<true>, grid, dim3(256), lds_bytes, (hipStream_t)stream, p);

@@ -154,7 +154,7 @@ int xps_colsum_f32(const float* X, int64_t ldx, int rows, int cols, float* out, 
  *          read by the backward entry point of the same shape and mode only; [ndir][T][B][4H] on most paths, member-major
  *          ([ndir][T][H/32][B][4][32]) on the cluster path when H % 32 == 0 (sequential HBM streams per workgroup)            */
 /* ------------------------------------------------------------------------- */
-/* 128 < H <= 512 (H % 4 == 0, B >= 128): cluster-persistent recurrence (csrc/xps_gru_cluster.hip): W_hh stays in the registers
+/* 256 < H <= 512 (H % 4 == 0, B >= 128): cluster-persistent recurrence (csrc/xps_gru_cluster.hip): W_hh stays in the registers
  * of a cluster of workgroups for the whole sequence, the members exchange h_t through `workspace` inside ONE launch.
  * xps_set_gru_cluster_mode / XPS_GRU_CLUSTER = off | steps | persistent (0 | 1 | 2, default 2): 1 runs the same kernels one
  * step per launch, 0 the per-step GEMM kernels.  A hand-off that timed out (3 s; e.g. two such launches of different processes
@@ -195,6 +195,31 @@ size_t xps_gru_seq_bwd_f32_workspace(int T, int B, int H, int ndir);
 int xps_gru_seq_bwd_f32(const float* dy, const float* dhn, const float* y_ext, const float* saved,
                         const float* const* w_hh, const float* const* w_hh_t, float* dgi, float* dghn, float* dh0,
                         int T, int B, int H, int ndir, void* workspace, size_t workspace_bytes, void* stream);
+/* Which kernels the two entry points above launch for a shape: the one dispatch decision both make, as a query (host logic
+ * only; it follows xps_set_gru_cluster_mode, XPS_GRU_STEP_PATH and the device's CU count like the launches do).
+ *   weights_aligned16  every W_hh pointer (forward) / every W_hh and W_hh^T pointer (backward) is 16-byte aligned.  A call
+ *                      decides from the pointers it streams: W_hh in the forward and in the per-step backward, W_hh^T in the
+ *                      backward of the other routes; `saved` has one layout on all routes but the cluster's, so a forward and
+ *                      a backward that land on different kernels of those routes still belong together.
+ *   backward           0: xps_gru_seq_fwd_f32, 1: xps_gru_seq_bwd_f32
+ * The answer assumes 16-byte aligned activation buffers (y_ext, dgi, dghn; the resident, generic-vector and cluster kernels
+ * require them; the per-step kernels drop VECA for a buffer that is not).
+ * Envelope.  XPS_GRU_ROUTE_REFUSED: both entry points return XPS_E_INVALID and write nothing.  The routes that keep a state /
+ * gradient tile in LDS (RESIDENT, GENERIC_*) stop at H = XPS_GRU_MAX_H_TILE in BOTH directions: the backward's tile, 16 trials
+ * x (4 Hp + 8) floats with Hp = H rounded up to 16, must fit 160 KiB.  They serve H <= 128, and larger H only with
+ * XPS_GRU_STEP_PATH=0.  The per-step kernels hold no tile; they stop at H = XPS_GRU_MAX_H_STEP in both directions, the largest
+ * H the forward has ever accepted and the largest the tests launch.  The cluster kernels serve 256 < H <= 512. */
+#define XPS_GRU_MAX_H_TILE 624
+#define XPS_GRU_MAX_H_STEP 1264
+#define XPS_GRU_ROUTE_REFUSED 0
+#define XPS_GRU_ROUTE_CLUSTER 1          /* csrc/xps_gru_cluster.hip, persistent or one step per launch */
+#define XPS_GRU_ROUTE_RESIDENT 2         /* H = 64 / 128, W_hh in registers */
+#define XPS_GRU_ROUTE_GENERIC_VEC 3      /* LDS-tile kernel, 16-byte weight loads */
+#define XPS_GRU_ROUTE_GENERIC_SCALAR 4   /* LDS-tile kernel, scalar weight loads (H % 4 != 0 or misaligned weights) */
+#define XPS_GRU_ROUTE_STEP 8             /* one launch per step; or-ed with the two flags below: 8 .. 11 */
+#define XPS_GRU_ROUTE_STEP_VECA 1        /* 16-byte loads of the activation operand (H % 4 == 0) */
+#define XPS_GRU_ROUTE_STEP_VECB 2        /* 16-byte loads of W_hh (H % 4 == 0 and aligned weights) */
+int xps_gru_seq_route(int T, int B, int H, int ndir, int weights_aligned16, int backward);
 /* Inter-layer dropout of a multi-layer GRU (torch.nn.GRU(dropout=p): nn_models/models.py:661-663, applied to the outputs of
  * every layer but the last) fused into the recurrence kernels of the register-resident shapes (H = 64 / 128;
  * xps_gru_seq_fused_dropout_supported says which): the forward kernel also writes y_drop (T x B x ndir*H) = y * keep / (1 - p)
