@@ -266,10 +266,13 @@ __global__ void gather_rows_kernel(const float* __restrict__ table, const long l
 // stage 1: block (strip of 64 columns, chunk of SC_CHUNK batch rows) accumulates into an LDS copy of the
 //          table (each thread owns one (row-group, column): no atomics) and writes its partial table;
 // stage 2: partial tables are summed in chunk order.
-constexpr int SC_CHUNK = 64, SC_MAXROWS = 16;
+// MR = table rows the LDS copy holds: 16 (the token tables of the models: at most 15 classes and the start token) or
+// SC_MAXROWS (a wider table, e.g. a decoder with more than 15 classes: 64 KiB of LDS, one block per CU fewer).
+constexpr int SC_CHUNK = 64, SC_SMALLROWS = 16, SC_MAXROWS = 64;
+template <int MR>
 __global__ __launch_bounds__(256) void scatter_rows_stage1(const float* __restrict__ dout, const long long* __restrict__ idx,
                                                            float* __restrict__ part, int B, int cols, int n_rows) {
-    __shared__ float tab[4][SC_MAXROWS][64];
+    __shared__ float tab[4][MR][64];
     const int l = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + l;
     for (int r = 0; r < n_rows; ++r) tab[q][r][l] = 0.f;
@@ -755,7 +758,7 @@ extern "C" size_t xps_scatter_rows_f32_workspace(int B, int cols, int n_rows) {
 extern "C" int xps_scatter_rows_f32(const float* dout, const int64_t* idx, float* dtable, int B, int cols, int n_rows,
                                     int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
     XPS_CHECK_ARG(dout && idx && dtable && B >= 0 && cols >= 1 && n_rows >= 1, "bad argument");
-    XPS_CHECK_ARG(n_rows <= SC_MAXROWS, "table has too many rows for the scatter kernel (max 16)");
+    XPS_CHECK_ARG(n_rows <= SC_MAXROWS, "table has too many rows for the scatter kernel (max 64)");
     if (workspace_bytes < xps_scatter_rows_f32_workspace(B, cols, n_rows) || !workspace) {
         xps_set_error("xps_scatter_rows_f32: workspace too small");
         return XPS_E_WORKSPACE;
@@ -763,8 +766,12 @@ extern "C" int xps_scatter_rows_f32(const float* dout, const int64_t* idx, float
     const int nchunks = B > 0 ? cdiv(B, SC_CHUNK) : 0;
     float* part = (float*)workspace;
     if (nchunks > 0) {
-        hipLaunchKernelGGL(scatter_rows_stage1, dim3(cdiv(cols, 64), nchunks), dim3(256), 0, (hipStream_t)stream,
-                           dout, (const long long*)idx, part, B, cols, n_rows);
+        if (n_rows <= SC_SMALLROWS)
+            hipLaunchKernelGGL(scatter_rows_stage1<SC_SMALLROWS>, dim3(cdiv(cols, 64), nchunks), dim3(256), 0, (hipStream_t)stream,
+                               dout, (const long long*)idx, part, B, cols, n_rows);
+        else
+            hipLaunchKernelGGL(scatter_rows_stage1<SC_MAXROWS>, dim3(cdiv(cols, 64), nchunks), dim3(256), 0, (hipStream_t)stream,
+                               dout, (const long long*)idx, part, B, cols, n_rows);
         XPS_CHECK_LAUNCH();
     }
     const long long total = (long long)n_rows * cols;

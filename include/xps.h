@@ -380,7 +380,7 @@ int xps_ctc_beam_readout(const void* state, size_t state_bytes, int B, int beam_
 /* out[b][:] = table[idx[b]][:]  (embedding / precomputed input projection rows) */
 int xps_gather_rows_f32(const float* table, const int64_t* idx, float* out,
                         int B, int cols, int n_rows, void* stream);
-/* dtable[r][:] (+)= sum_{b: idx[b]==r} dout[b][:]  (deterministic two-stage; n_rows <= 16) */
+/* dtable[r][:] (+)= sum_{b: idx[b]==r} dout[b][:]  (deterministic two-stage; n_rows <= 64) */
 size_t xps_scatter_rows_f32_workspace(int B, int cols, int n_rows);
 int xps_scatter_rows_f32(const float* dout, const int64_t* idx, float* dtable,
                          int B, int cols, int n_rows, int accumulate,

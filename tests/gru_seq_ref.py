@@ -106,6 +106,12 @@ def step_ref(gi_t, w_hh, b_hh, h_prev):
 def step_bound(parts, mode, activation):
     """Elementwise bound (B, H) on |kernel's h_t - step_ref| given the same h_{t-1}; mode 'fp32' | 'bf16x3',
     activation 'libm' | 'hw' (module docstring)."""
+    return gate_bounds(parts, mode, activation)['h']
+
+
+def gate_bounds(parts, mode, activation):
+    """The intermediate bounds of the module docstring next to the final one: {'r', 'z', 'q', 'n', 'h'} -> (B, H), for
+    kernels that store r, z, n and q = W_hn h + b_hn (the `saved` tensors).  ['h'] is step_bound."""
     gi, gh, bh = np.abs(parts['gi']), np.abs(parts['gh']), np.abs(parts['bh'])
     r, z, n, q, h = parts['r'], parts['z'], parts['n'], parts['q'], parts['h']
     D = DOT[mode] * parts['gh_abs']
@@ -121,7 +127,7 @@ def step_bound(parts, mode, activation):
     dq = D[2] + U * (gh[2] + bh[2])
     dan = r * dq + np.abs(q) * dr + dr * dq + 3 * U * (gi[2] + r * np.abs(q))
     dn = (1 - n * n) * dan + TANH2 * dan ** 2 + A_n
-    return (1 - z) * dn + np.abs(h - n) * dz + dz * dn + 4 * U
+    return dict(r=dr, z=dz, q=dq, n=dn, h=(1 - z) * dn + np.abs(h - n) * dz + dz * dn + 4 * U)
 
 
 def _slots(t, d):

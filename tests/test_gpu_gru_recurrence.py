@@ -47,12 +47,10 @@ import pytest
 import torch
 
 import gru_seq_ref as R
+from guarded_buf import F32, Buf
 
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
-SENT = 0x7FC0DEAD                    # a quiet-NaN bit pattern no kernel produces
-G = 64                               # guard floats on each side of a buffer (256 bytes: the data stays 16-byte aligned)
 INVALID = -1                         # XPS_E_INVALID
 S3 = R.STEP | R.STEP_VECA | R.STEP_VECB
 SAT_BWD_MAX_T = 8                    # the saturating regime's backward is checked up to this T (module docstring)
@@ -73,41 +71,6 @@ def _built():
     from cross_patient_speech_decoding_amd import _build
     _build.build(verbose=False)
     assert torch.cuda.is_available(), 'gpu tests need the MI355X'
-
-
-class Buf:
-    """n float32 between two guard rows of G floats; off = 1 starts the data 4 bytes past a 16-byte boundary."""
-
-    def __init__(self, n, fill_bits=None, data=None, off=0):
-        self.n, self.lo = int(n), G + off
-        total = self.lo + self.n + G
-        if data is None:
-            self.buf = torch.full((total,), SENT if fill_bits is None else fill_bits, dtype=torch.int32, device='cuda').view(torch.float32)
-        else:
-            self.buf = torch.full((total,), float('nan'), dtype=torch.float32, device='cuda')
-            self.buf[self.lo:self.lo + self.n] = torch.from_numpy(np.array(data, F32).ravel()).cuda()
-            self.before = self.bits().clone()
-        self.ptr = self.buf.data_ptr() + 4 * self.lo
-        assert self.ptr % 16 == 4 * off
-
-    def bits(self):
-        return self.buf.view(torch.int32)
-
-    def view(self):
-        return self.buf[self.lo:self.lo + self.n]
-
-    def numpy(self, shape):
-        return self.view().cpu().numpy().reshape(shape)
-
-    def guards_intact(self):
-        b = self.bits()
-        return bool((b[:self.lo] == SENT).all()) and bool((b[self.lo + self.n:] == SENT).all())
-
-    def untouched(self):
-        return bool((self.bits() == SENT).all())
-
-    def unchanged(self):
-        return torch.equal(self.bits(), self.before)
 
 
 def _ptrs(bufs):

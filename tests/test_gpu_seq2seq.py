@@ -171,7 +171,7 @@ def test_reference_coin_sequence_is_reproduced():
 
 
 @pytest.mark.parametrize('H,B', [(64, 37), (128, 50)])
-def test_fused_decoder_equals_composed_path_and_oracle(H, B):
+def test_fused_decoder_equals_composed_path_and_oracle(H, B, gemm_precision):
     """The one-launch decoder (xps_decoder_*) against the composed per-step path of the same model and
     against the CPU oracle: logits, argmax, and every parameter gradient, mixed teacher forcing."""
     from oracle.seq2seq_oracle import Seq2SeqOracle
