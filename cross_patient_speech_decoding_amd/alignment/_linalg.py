@@ -745,7 +745,7 @@ def pinv_small(M):
 # ------------------------------------------------------------------------------------ fold-batched tables
 # The grouped kernels (csrc/xps_fold_align.hip) read device tables of int64 words and trust them: every extent is checked
 # here, against the tensors themselves, before a table is uploaded.
-XCOV_WORDS, APPLY_WORDS, CNDAVG_WORDS = 20, 12, 8             # XPS_*_WORDS of include/xps.h
+XCOV_WORDS, APPLY_WORDS, CNDAVG_WORDS, GRAM_WORDS = 20, 12, 8, 8  # XPS_*_WORDS of include/xps.h
 XCOV_SPLIT_ROWS, XCOV_MAX_SPLITS = 256, 64
 
 
@@ -869,6 +869,39 @@ def apply_grouped(entries):
     tab_d = torch.from_numpy(tab.reshape(-1)).to(dev)
     tiles_d = torch.from_numpy(tiles).to(dev)
     call('xps_apply_grouped_f64', tab_d.data_ptr(), n, tiles_d.data_ptr(), len(tiles), stream())
+
+
+def gram_tiles(rows):
+    """The int32 tile table of a grouped Gram launch (pure numpy): one row {problem, ti, tj} for every 64 x 64 tile with tj <= ti of
+    every problem, problems in order, ti ascending and tj ascending inside it.  rows[p]: problem p's row count."""
+    out = []
+    for p, n in enumerate(rows):
+        ti, tj = np.tril_indices(-(-int(n) // 64))
+        out.append(np.stack([np.full(len(ti), p), ti, tj], axis=1))
+    return np.ascontiguousarray(np.concatenate(out) if out else np.zeros((0, 3)), dtype=np.int32)
+
+
+def gram_grouped(problems):
+    """problems: list of (V, G): G[:] = V @ V.T for every problem in ONE xps_gram_grouped_f64 launch.  V (n, D) float32 / float64,
+    G (n, n) float64 -- device matrices with contiguous rows (slices of larger tensors are fine); n and D differ per problem and
+    may be 0.  Every G is symmetric bit for bit.  Returns the host tables of the call, which the caller keeps until it has
+    synchronised with the stream (the library checks them once more and copies them on the stream)."""
+    n = len(problems)
+    if n == 0:
+        return None
+    tab = np.zeros((n, GRAM_WORDS), dtype=np.int64)
+    for i, (V, G) in enumerate(problems):
+        _check_matrix(V, 'gram_grouped V')
+        _check_matrix(G, 'gram_grouped G')
+        rows, D = V.shape
+        if G.dtype != F64 or tuple(G.shape) != (rows, rows) or rows >= 2 ** 31 - 64 or D >= 2 ** 31 - 16:
+            raise ValueError('gram_grouped: G must be the float64 (n, n) matrix of the (n, D) matrix V')
+        tab[i, :7] = [V.data_ptr(), _is32(V), V.stride(0), rows, D, G.data_ptr(), G.stride(0)]
+    tab, tiles = np.ascontiguousarray(tab.reshape(-1)), gram_tiles(tab[:, 3])
+    nb = int(lib().xps_gram_grouped_f64_workspace(n, len(tiles)))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=device())
+    call('xps_gram_grouped_f64', tab.ctypes.data, n, tiles.ctypes.data, len(tiles), ws.data_ptr(), nb, stream())
+    return tab, tiles, ws
 
 
 def cnd_avg_folds(segments):

@@ -22,6 +22,8 @@ Jacobi launches -- one per distinct matrix size -- and the chunks of ``max_bytes
   7  xps_xcov_grouped_f64     C_aa, C_bb, C_ab of every (fold, patient)
   8  Jacobi                   C_aa / C_bb by size, then the whitened K matrices by shape
   9  xps_apply_grouped_f64    every (fold, patient) aligned block into its slab of the fold's pooled tensor
+With ``append_heldout=True`` every fold's pooled tensor has the fold's held-out trials after the pooled rows; they are more
+entries of launch 5 (the fold's own mean and components), so the list above does not grow.
 The O(d^2) glue (whitening factors, M_a, M_b, the maps) is host numpy, as in ``AlignCCA._cca_device``.
 
 Only ``AlignCCA``'s defaults (type='class', return_space='b_to_a') are supported.
@@ -46,6 +48,15 @@ def _csr(inv, n):
     order = np.argsort(inv, kind='stable').astype(np.int64)
     start = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=n))]).astype(np.int64)
     return order, start
+
+
+def _runs(idx):
+    """[(first trial, count, position)]: `idx` cut into runs of consecutive trials."""
+    if len(idx) == 0:
+        return []
+    first = np.concatenate([[0], np.flatnonzero(np.diff(idx) != 1) + 1])
+    count = np.diff(np.concatenate([first, [len(idx)]]))
+    return [(int(idx[a]), int(c), int(a)) for a, c in zip(first, count)]
 
 
 class FoldPlan:
@@ -102,10 +113,7 @@ def fold_plan(y_align, pool_align_labels, splits):
         plan.cond_start.append(start)
         plan.shared.append([tuple(np.intersect1d(uniq, pk, assume_unique=True, return_indices=True)[1:])
                             for pk in plan.pool_keys])
-        cut = np.flatnonzero(np.diff(tr) != 1) + 1
-        first = np.concatenate([[0], cut])
-        count = np.diff(np.concatenate([first, [len(tr)]]))
-        plan.train_runs.append([(int(tr[a]), int(c), int(a)) for a, c in zip(first, count)])
+        plan.train_runs.append(_runs(tr))
     return plan
 
 
@@ -134,6 +142,14 @@ class FoldAlignment:
         """Pooled float32 device tensor of fold f: the target's training trials in `train` order, then each aligned
         pooled patient in order -- ``process_aligner``'s X_pool."""
         return self._pool[f]
+
+    def pool_with_heldout(self, f):
+        """(rows, held-out trials) of a fit with ``append_heldout=True``: the float32 device tensor whose first rows are
+        ``train_pool(f)`` and whose last len(held-out) rows are the fold's held-out target trials in fold f's latent space
+        (``project(f, held-out)``, bit for bit), and the original indices of those trials, in the order of the rows."""
+        if self._pool_all is None:
+            raise ValueError('pool_with_heldout: the folds were fitted without append_heldout=True')
+        return self._pool_all[f], self.plan.splits[f][1]
 
     def project(self, f, idx):
         """Target trials `idx` in fold f's latent space, float32 device tensor (len(idx), T, n_components_[f])."""
@@ -189,12 +205,14 @@ def _solve_cca(probs):
             p['map'] = p['M_b'] @ np.linalg.pinv(p['M_a'])
 
 
-def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 30):
+def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 30, append_heldout=False):
     """Fit the target PCA and the P pairwise CCA alignments of EVERY fold of `splits` at once.
 
     X (N, T, C) float32 / float64 tensor or ndarray; y_align the target's alignment labels; pool_data the list of
     (x, y, y_align) the data modules take; splits as ``fold_plan`` requires.  Folds are processed in chunks whose
-    per-fold device arrays (Z_f and the pooled tensor) stay within `max_bytes`.  Returns a ``FoldAlignment``."""
+    per-fold device arrays (Z_f and the pooled tensor) stay within `max_bytes`.  ``append_heldout``: every fold's pooled tensor is
+    allocated with room for the fold's held-out trials after the pooled rows and launch 5 fills them (``pool_with_heldout``);
+    ``train_pool`` and everything else are what they are without it.  Returns a ``FoldAlignment``."""
     Xd = LA.to_device(X)
     if Xd.dim() != 3:
         raise ValueError('fit_folds: X must be (trials, time, channels)')
@@ -262,23 +280,29 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
 
     n_train = [len(tr) for tr, _ in plan.splits]
     pool_rows = [n + sum(pool_n) for n in n_train]
+    held_rows = [len(te) if append_heldout else 0 for _, te in plan.splits]
     fa._pool = [None] * F
+    fa._pool_all = [None] * F if append_heldout else None
     fa.M_a_ = [[None] * P for _ in range(F)]
     fa.M_b_ = [[None] * P for _ in range(F)]
     fa.canon_corrs_ = [[None] * P for _ in range(F)]
     fa.maps_ = [[None] * P for _ in range(F)]
     fa.fallbacks_ = []
-    per_fold = [N * T * kf[f] * 8 + pool_rows[f] * T * kf[f] * 4 for f in range(F)]
+    per_fold = [N * T * kf[f] * 8 + (pool_rows[f] + held_rows[f]) * T * kf[f] * 4 for f in range(F)]
     for chunk in _fold_chunks(per_fold, max_bytes):
         # 5: Z_f and the target rows of the pooled tensors
         Z, entries = {}, []
         for f in chunk:
             Z[f] = torch.empty(N * T, kf[f], dtype=LA.F64, device=Xd.device)
-            fa._pool[f] = torch.empty(pool_rows[f], T, kf[f], dtype=torch.float32, device=Xd.device)
+            whole = torch.empty(pool_rows[f] + held_rows[f], T, kf[f], dtype=torch.float32, device=Xd.device)
+            fa._pool[f] = whole[:pool_rows[f]]
             entries.append((X2, fa._mean_d[f], fa._W_d[f], Z[f]))
-            p2 = fa._pool[f].view(-1, kf[f])
-            entries += [(X2[a * T:(a + cnt) * T], fa._mean_d[f], fa._W_d[f], p2[dst * T:(dst + cnt) * T])
-                        for a, cnt, dst in plan.train_runs[f]]
+            p2 = whole.view(-1, kf[f])
+            runs = plan.train_runs[f]
+            if append_heldout:
+                fa._pool_all[f] = whole
+                runs = runs + [(a, cnt, pool_rows[f] + dst) for a, cnt, dst in _runs(plan.splits[f][1])]
+            entries += [(X2[a * T:(a + cnt) * T], fa._mean_d[f], fa._W_d[f], p2[dst * T:(dst + cnt) * T]) for a, cnt, dst in runs]
         LA.apply_grouped(entries)
         # 6: condition means of every fold
         A, segs = {}, []

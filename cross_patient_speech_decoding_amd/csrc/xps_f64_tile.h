@@ -1,5 +1,6 @@
-// The float64 MFMA tile of the alignment kernels, once: gemm_f64_kernel (xps_align.hip), xcov_grouped_kernel and
-// apply_grouped_kernel (xps_fold_align.hip) are built from these pieces and keep only their table decoding, side sums and stores.
+// The float64 MFMA tile of the alignment kernels, once: gemm_f64_kernel (xps_align.hip), xcov_grouped_kernel,
+// apply_grouped_kernel and gram_grouped_kernel (xps_fold_align.hip) are built from these pieces and keep only their table
+// decoding, side sums and stores.
 //
 // A workgroup of 256 threads (4 waves) owns 64 x 64 outputs and walks the contraction in steps of 16: both operands are staged
 // to LDS as S[k][x] (16 x 64, rows padded to 66 doubles: 2 x 16 x 66 x 8 = 16896 bytes), fp32 / fp64 elements converted and

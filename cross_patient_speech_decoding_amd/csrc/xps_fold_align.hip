@@ -9,9 +9,13 @@
 //  xps_loo_sum_f64         out[f] = sum over g != f of in[g], ascending g, plain adds.
 //  xps_apply_grouped_f64   a table of (X - mean) W products with ragged widths in one launch (xps_apply_f64's arithmetic).
 //  xps_cnd_avg_folds_f64   a table of segment means: fp64 sums over listed trials in list order.
+//  xps_gram_grouped_f64    a table of Gram matrices G_p = V_p V_p^T with ragged row counts and contraction lengths in one launch:
+//                          one workgroup per 64 x 64 tile of the lower triangle, the contraction walked whole in ascending k,
+//                          off-diagonal tiles mirrored, so every G_p is symmetric bit for bit and the same for any grid.
 //
 // The tables are DEVICE arrays of int64 words built by the caller (alignment/_linalg.py checks every extent against the
-// tensors it was given before it uploads one); the kernels trust them.
+// tensors it was given before it uploads one); the kernels trust them.  xps_gram_grouped_f64 alone takes HOST tables: its entry
+// checks them and copies them to the device on the stream.
 #include "xps_common.h"
 #include "xps_f64_tile.h"
 
@@ -27,6 +31,9 @@ static_assert(AP_WORDS_USED <= XPS_APPLY_GROUPED_WORDS, "entry words");
 // words of one xps_cnd_avg_folds_f64 segment
 enum { CS_SRC, CS_ROWLEN, CS_OUT, CS_BEGIN, CS_END, CS_WORDS_USED };
 static_assert(CS_WORDS_USED <= XPS_CND_AVG_FOLDS_WORDS, "segment words");
+// words of one xps_gram_grouped_f64 problem
+enum { GG_V, GG_V32, GG_LDV, GG_N, GG_D, GG_G, GG_LDG, GG_WORDS_USED };
+static_assert(GG_WORDS_USED <= XPS_GRAM_GROUPED_WORDS, "problem words");
 
 // Storage row of contraction index k of a problem: row k % blk_len of block k / blk_len of its list of K / blk_len blocks.
 struct BlockRows {
@@ -152,6 +159,41 @@ __global__ void cnd_avg_folds_kernel(const long long* __restrict__ segs, const i
     out[e] = acc / (double)(en - b);
 }
 
+// One workgroup per (problem, 64-row tile ti, 64-column tile tj <= ti); tiles[3 t ..] = {problem, ti, tj}.  Both operands are row
+// blocks of V, staged contraction-contiguous.  An off-diagonal tile is stored to (ti, tj) and, transposed, to (tj, ti); a diagonal
+// tile is stored as computed: its elements (i, j) and (j, i) are sums of the same products in the same order (k ascending).
+__global__ __launch_bounds__(256) void gram_grouped_kernel(const long long* __restrict__ probs, const int* __restrict__ tiles) {
+    __shared__ __attribute__((aligned(16))) double As[DK][DLD];
+    __shared__ __attribute__((aligned(16))) double Bs[DK][DLD];
+    const int* tl = tiles + 3 * (long long)blockIdx.x;
+    const long long* P = probs + (long long)tl[0] * XPS_GRAM_GROUPED_WORDS;
+    const Mat64 V{reinterpret_cast<const void*>(P[GG_V]), P[GG_LDV], nullptr, (int)P[GG_V32]};
+    const int n = (int)P[GG_N], D = (int)P[GG_D];
+    double* G = reinterpret_cast<double*>(P[GG_G]);
+    const long long ldg = P[GG_LDG];
+
+    const int tid = threadIdx.x;
+    const int m0 = tl[1] * DM, n0 = tl[2] * DN;
+    const bool mirror = m0 != n0;
+
+    f64x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = (f64x4){0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < D; k0 += DK) {
+        stage_kc(V, As, m0, n, k0, D, tid);
+        stage_kc(V, Bs, n0, n, k0, D, tid);
+        __syncthreads();
+        mfma_f64_tile(As, Bs, acc, tid);
+        __syncthreads();
+    }
+    store_f64_tile(acc, m0, n0, n, n, tid, [&](int row, int col, double v) {
+        G[(long long)row * ldg + col] = v;
+        if (mirror) G[(long long)col * ldg + row] = v;
+    });
+}
+
+inline size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
+
 }  // namespace
 
 extern "C" int xps_xcov_grouped_f64(const int64_t* problems, int n_problems, const int32_t* tiles, int n_tiles, int max_out_len,
@@ -198,6 +240,47 @@ extern "C" int xps_cnd_avg_folds_f64(const int64_t* segments, int n_segments, co
     XPS_CHECK_ARG(n_segments <= 65535, "more than 65535 segments in one call");
     hipLaunchKernelGGL(cnd_avg_folds_kernel, dim3(cdiv(max_row_len, 256), n_segments), dim3(256), 0, (hipStream_t)stream,
                        (const long long*)segments, (const int*)trials);
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}
+
+extern "C" size_t xps_gram_grouped_f64_workspace(int n_problems, int n_tiles) {
+    if (n_problems < 0 || n_tiles < 0) return 0;
+    return align8(sizeof(long long) * XPS_GRAM_GROUPED_WORDS * (size_t)n_problems) + align8(3 * sizeof(int) * (size_t)n_tiles);
+}
+
+extern "C" int xps_gram_grouped_f64(const int64_t* problems, int n_problems, const int32_t* tiles, int n_tiles, void* ws,
+                                    size_t ws_bytes, void* stream) {
+    XPS_CHECK_ARG(n_problems >= 0 && n_tiles >= 0, "negative count");
+    if (n_problems == 0 && n_tiles == 0) return XPS_OK;
+    XPS_CHECK_ARG((problems || n_problems == 0) && (tiles || n_tiles == 0), "null table");
+    for (int p = 0; p < n_problems; ++p) {                         // both tables are HOST arrays: checked here, then copied
+        const int64_t* P = problems + (size_t)XPS_GRAM_GROUPED_WORDS * p;
+        XPS_CHECK_ARG(P[GG_N] >= 0 && P[GG_D] >= 0, "negative count");
+        XPS_CHECK_ARG(P[GG_N] <= INT32_MAX - DM && P[GG_D] <= INT32_MAX - DK, "n or D beyond int32");
+        XPS_CHECK_ARG(P[GG_V32] == 0 || P[GG_V32] == 1, "v_is_f32 must be 0 or 1");
+        XPS_CHECK_ARG(P[GG_LDV] >= P[GG_D], "ldv < D");
+        XPS_CHECK_ARG(P[GG_LDG] >= P[GG_N], "ldg < n");
+        XPS_CHECK_ARG(P[GG_N] == 0 || (P[GG_G] != 0 && (P[GG_V] != 0 || P[GG_D] == 0)), "null matrix");
+    }
+    for (int t = 0; t < n_tiles; ++t) {
+        const int32_t* tl = tiles + 3 * (size_t)t;
+        XPS_CHECK_ARG(tl[0] >= 0 && tl[0] < n_problems, "a tile names no problem");
+        const int64_t n = problems[(size_t)XPS_GRAM_GROUPED_WORDS * tl[0] + GG_N];
+        XPS_CHECK_ARG(tl[2] >= 0 && tl[2] <= tl[1], "a tile above the diagonal (tj <= ti is needed)");
+        XPS_CHECK_ARG((int64_t)tl[1] * DM < n, "a tile origin at or past n");
+    }
+    if (n_tiles == 0) return XPS_OK;
+    XPS_CHECK_ARG(ws, "null workspace");
+    XPS_CHECK_ARG(ws_bytes >= xps_gram_grouped_f64_workspace(n_problems, n_tiles), "workspace too small");
+    static_assert(sizeof(long long) == sizeof(int64_t), "the table is read as long long");
+    hipStream_t st = (hipStream_t)stream;
+    long long* probs_d = static_cast<long long*>(ws);
+    int* tiles_d = reinterpret_cast<int*>(static_cast<char*>(ws) + align8(sizeof(long long) * XPS_GRAM_GROUPED_WORDS * (size_t)n_problems));
+    hipError_t e = hipMemcpyAsync(probs_d, problems, sizeof(long long) * XPS_GRAM_GROUPED_WORDS * (size_t)n_problems, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(tiles_d, tiles, 3 * sizeof(int) * (size_t)n_tiles, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { xps_set_error("%s: copying the tables failed: %s", __func__, hipGetErrorString(e)); return XPS_E_HIP; }
+    hipLaunchKernelGGL(gram_grouped_kernel, dim3(n_tiles), dim3(256), 0, st, (const long long*)probs_d, (const int*)tiles_d);
     XPS_CHECK_LAUNCH();
     return XPS_OK;
 }

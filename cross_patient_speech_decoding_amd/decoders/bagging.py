@@ -64,6 +64,20 @@ def bagging_sample_indices(random_state, n_estimators, n_samples, n_features, ma
     return out
 
 
+def sample_weights(samples, base_w, bootstrap=True):
+    """The ``sample_weight`` sklearn's bagging hands to each estimator's fit (host only): ``base_w`` times the multiplicity of a row
+    in the estimator's draws, or, without replacement, ``base_w`` on the drawn rows and zero elsewhere."""
+    n = len(base_w)
+    if bootstrap:
+        return [base_w * np.bincount(s, minlength=n) for s in samples]
+    weights = []
+    for s in samples:
+        mask = np.zeros(n, dtype=bool)
+        mask[s] = True
+        weights.append(np.where(mask, base_w, 0.0))
+    return weights
+
+
 class BaggingClassifier(ClassifierMixin, BaseEstimator):
     """``sklearn.ensemble.BaggingClassifier`` for ``estimator=decoders.SVC(...)``, trained and evaluated as ONE device problem.
 
@@ -128,14 +142,7 @@ class BaggingClassifier(ClassifierMixin, BaseEstimator):
             raise ValueError(f'the vote kernel takes 2..64 classes; got {k}')
         # the draws (host), then the weights sklearn would hand to each estimator's fit
         samples = bagging_sample_indices(self.random_state, E, n, d, self.max_samples, self.bootstrap)
-        if self.bootstrap:
-            weights = [base_w * np.bincount(s, minlength=n) for s in samples]
-        else:
-            weights = []
-            for s in samples:
-                mask = np.zeros(n, dtype=bool)
-                mask[s] = True
-                weights.append(np.where(mask, base_w, 0.0))
+        weights = sample_weights(samples, base_w, self.bootstrap)
         # everything that SVC.fit derives from the X / y it is handed is derived from the WHOLE X / y, as under sklearn's bagging
         gamma = _ovo.gamma_value(est.kernel, est.gamma, X)
         cw = _ovo.class_weights(est.class_weight, classes, yi)

@@ -376,6 +376,42 @@ def _cat(dicts, key):
     return np.concatenate([d[key] for d in dicts])
 
 
+def solve_and_score(Kbuf, models, mn, mbase, tol, svc_max_iter, k):
+    """The models (dicts with problems, C, test_pos, ytest) whose kernel matrices lie in the flat buffer ``Kbuf``, model s's a square
+    matrix of mn[s] rows at element mbase[s]: three uploads (index lists, matrix offsets and leading dimensions, bounds), ONE
+    ``xps_svm_smo_multi_f64`` over all class-pair problems, ONE ``xps_svm_cv_score_f64`` and one download.  Returns
+    (conf (S, k, k), pred, tst_off): model s's predictions of its held-out rows are pred[tst_off[s]:tst_off[s + 1]]."""
+    dev = Kbuf.device
+    S = len(models)
+    probs = [mod['problems'] for mod in models]
+    nprob = np.array([len(p['npos']) for p in probs], dtype=np.int64)
+    mn, mbase = np.asarray(mn, dtype=np.int64), np.asarray(mbase, dtype=np.int64)
+    sizes_q = _cat(probs, 'sizes')
+    off = np.concatenate([[0], np.cumsum(sizes_q)])
+    tst_off = np.concatenate([[0], np.cumsum([len(mod['test_pos']) for mod in models])])
+    mod_off = np.concatenate([[0], np.cumsum(nprob)])
+    if max(off[-1], tst_off[-1]) > np.iinfo(np.int32).max:
+        raise ValueError('the chunk holds more training points than int32 offsets address: lower max_kernel_bytes')
+    Q, T = int(mod_off[-1]), int(tst_off[-1])
+    idx_d, off_d, npos_d, pa_d, pb_d, tst_d, yt_d, mn_d = _ovo.upload_int32(
+        [_cat(probs, 'idx'), off, _cat(probs, 'npos'), _cat(probs, 'pair_a'), _cat(probs, 'pair_b'), _cat(models, 'test_pos'),
+         _cat(models, 'ytest'), mn], dev)
+    longs_d = torch.from_numpy(np.concatenate([np.repeat(mbase, nprob), np.repeat(mn, nprob), mbase, mn])).to(dev)
+    kbase_d, kld_d, mbase_d, mld_d = longs_d[:Q], longs_d[Q:2 * Q], longs_d[2 * Q:2 * Q + S], longs_d[2 * Q + S:]
+    cb = np.concatenate([_ovo.bounds(mod['C'], mod['problems']) for mod in models])
+    alpha, rho, _ = _ovo.smo(Kbuf, idx_d, off_d, npos_d, int(sizes_q.max()), cb, tol, svc_max_iter, kbase_d, kld_d)
+    out = torch.empty(S * k * k + max(T, 1), dtype=torch.int32, device=dev)                     # conf, then pred: one download
+    ws_bytes = int(lib().xps_svm_cv_score_f64_workspace(S))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    mod_off_h, tst_off_h = mod_off.astype(np.int32), tst_off.astype(np.int32)                   # host arrays of the call
+    call('xps_svm_cv_score_f64', Kbuf.data_ptr(), mbase_d.data_ptr(), mld_d.data_ptr(), mn_d.data_ptr(), idx_d.data_ptr(), off_d.data_ptr(),
+         npos_d.data_ptr(), alpha.data_ptr(), rho.data_ptr(), pa_d.data_ptr(), pb_d.data_ptr(), mod_off_h.ctypes.data, tst_d.data_ptr(),
+         yt_d.data_ptr(), tst_off_h.ctypes.data, S, k, out.data_ptr() + 4 * S * k * k, out.data_ptr(), None, 0, ws.data_ptr(), ws_bytes,
+         stream())
+    host = out.cpu().numpy()                                    # (synchronises: the host offset arrays were read before this returns)
+    return host[:S * k * k].reshape(S, k, k), host[S * k * k:S * k * k + T], tst_off
+
+
 def _run_chunk(plan, mats, kernel, tol, svc_max_iter, k):
     """Kernel matrices ``mats`` (adjacent per view) and all their models: per view an upload, a Gram product and, for rbf, one
     multi-gamma launch; then one SMO launch, one scoring launch and one download.  Returns (models, conf (S, k, k), pred, tst_off)."""
@@ -410,35 +446,9 @@ def _run_chunk(plan, mats, kernel, tol, svc_max_iter, k):
     tables = LA.prefix_kernels([(plan.pca['Z'][f], sorted(cuts.items())) for f, cuts in prefixes.items()], kernel == 'rbf', Kbuf)  # noqa: F841
     models = [mod for mod in plan.models if mod['matrix'] in slot]
     models.sort(key=lambda mod: slot[mod['matrix']])            # (stable: plan order inside a matrix)
-    S = len(models)
-    probs = [mod['problems'] for mod in models]
-    nprob = np.array([len(p['npos']) for p in probs], dtype=np.int64)
-    mn = np.array([plan.rows(plan.matrices[mod['matrix']][0]) for mod in models], dtype=np.int64)
-    mbase = np.array([base[slot[mod['matrix']]] for mod in models], dtype=np.int64)
-    sizes_q = _cat(probs, 'sizes')
-    off = np.concatenate([[0], np.cumsum(sizes_q)])
-    tst_off = np.concatenate([[0], np.cumsum([len(mod['test_pos']) for mod in models])])
-    mod_off = np.concatenate([[0], np.cumsum(nprob)])
-    if max(off[-1], tst_off[-1]) > np.iinfo(np.int32).max:
-        raise ValueError('the chunk holds more training points than int32 offsets address: lower max_kernel_bytes')
-    Q, T = int(mod_off[-1]), int(tst_off[-1])
-    idx_d, off_d, npos_d, pa_d, pb_d, tst_d, yt_d, mn_d = _ovo.upload_int32(
-        [_cat(probs, 'idx'), off, _cat(probs, 'npos'), _cat(probs, 'pair_a'), _cat(probs, 'pair_b'), _cat(models, 'test_pos'),
-         _cat(models, 'ytest'), mn], dev)
-    longs_d = torch.from_numpy(np.concatenate([np.repeat(mbase, nprob), np.repeat(mn, nprob), mbase, mn])).to(dev)
-    kbase_d, kld_d, mbase_d, mld_d = longs_d[:Q], longs_d[Q:2 * Q], longs_d[2 * Q:2 * Q + S], longs_d[2 * Q + S:]
-    cb = np.concatenate([_ovo.bounds(mod['C'], mod['problems']) for mod in models])
-    alpha, rho, _ = _ovo.smo(Kbuf, idx_d, off_d, npos_d, int(sizes_q.max()), cb, tol, svc_max_iter, kbase_d, kld_d)
-    out = torch.empty(S * k * k + max(T, 1), dtype=torch.int32, device=dev)                     # conf, then pred: one download
-    ws_bytes = int(lib().xps_svm_cv_score_f64_workspace(S))
-    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
-    mod_off_h, tst_off_h = mod_off.astype(np.int32), tst_off.astype(np.int32)                   # host arrays of the call
-    call('xps_svm_cv_score_f64', Kbuf.data_ptr(), mbase_d.data_ptr(), mld_d.data_ptr(), mn_d.data_ptr(), idx_d.data_ptr(), off_d.data_ptr(),
-         npos_d.data_ptr(), alpha.data_ptr(), rho.data_ptr(), pa_d.data_ptr(), pb_d.data_ptr(), mod_off_h.ctypes.data, tst_d.data_ptr(),
-         yt_d.data_ptr(), tst_off_h.ctypes.data, S, k, out.data_ptr() + 4 * S * k * k, out.data_ptr(), None, 0, ws.data_ptr(), ws_bytes,
-         stream())
-    host = out.cpu().numpy()                                    # (synchronises: the host offset arrays were read before this returns)
-    return models, host[:S * k * k].reshape(S, k, k), host[S * k * k:S * k * k + T], tst_off
+    mn = [plan.rows(plan.matrices[mod['matrix']][0]) for mod in models]
+    mbase = [base[slot[mod['matrix']]] for mod in models]
+    return (models,) + solve_and_score(Kbuf, models, mn, mbase, tol, svc_max_iter, k)
 
 
 class SVCSearchCV(BaseEstimator):

@@ -593,6 +593,21 @@ int xps_apply_grouped_f64(const int64_t* entries, int n_entries, const int32_t* 
 #define XPS_CND_AVG_FOLDS_WORDS 8
 int xps_cnd_avg_folds_f64(const int64_t* segments, int n_segments, const int32_t* trials, int64_t max_row_len,
                           void* stream);
+/* n_problems Gram matrices  G_p = V_p V_p^T  in one launch (decoders/fold_decode.py: the kernel matrix of every fold of a
+ * cross-validated aligned decode).  V_p is row-major float32 or float64, n rows of D contraction elements, leading dimension
+ * ldv >= D; G_p float64 n x n, leading dimension ldg >= n; n and D differ per problem.  Words of a problem
+ * (XPS_GRAM_GROUPED_WORDS each): 0 V, 1 v_is_f32, 2 ldv, 3 n, 4 D, 5 G, 6 ldg.  tiles: int32[3 * n_tiles] = {problem, 64-row tile
+ * ti, 64-column tile tj} for every tile with tj <= ti of every problem; one workgroup per tile walks the whole contraction in
+ * ascending k on the f64 MFMA and stores an off-diagonal tile to (ti, tj) and, transposed, to (tj, ti): G_p is symmetric bit for
+ * bit and does not depend on the grid.  No atomics.  Elements of G_p beyond column n of a row are not written; D = 0 gives zeros.
+ * Both tables are HOST arrays: the call checks them (null tables, negative counts, ldv < D, ldg < n, null matrices, a tile that
+ * names no problem, lies above the diagonal or starts at or past n: XPS_E_INVALID before any launch; so a problem with n = 0 has
+ * no tiles and writes nothing) and copies them into ws (DEVICE, xps_gram_grouped_f64_workspace(...) bytes) on the stream; they
+ * must stay valid until the stream has passed the call.  Nothing synchronises. */
+#define XPS_GRAM_GROUPED_WORDS 8
+size_t xps_gram_grouped_f64_workspace(int n_problems, int n_tiles);
+int xps_gram_grouped_f64(const int64_t* problems, int n_problems, const int32_t* tiles, int n_tiles, void* ws, size_t ws_bytes,
+                         void* stream);
 /* Fold-batched PCA in front of the SVC search (decoders/search.py, batch_pca=True: the DimRedReshape(PCA) step of
  * scripts/aligned_decode_svm_ncv.py:171-177 for all folds and all n_components at once).
  *
