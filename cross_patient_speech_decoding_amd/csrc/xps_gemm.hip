@@ -802,114 +802,229 @@ inline int big_split_rows(int M, int tiles_per_row_tile) {
     return (int)(mb * xps_big::TM);
 }
 
-template <bool AK, bool BK>
+// ---- the dispatch decision of nt / nn / nn2 / nt_multi ------------------------------------------------------------------------
+// One launch: `code` names exactly one kernel instantiation (xps.h: XPS_GEMM_ROUTE_*), `grid` its blocks.  lead_rows < M: the
+// launch covers the leading rows only (big_split_rows) and the rows behind them are routed again by the same function.
+// route_gemm / route_gemm_multi are the only places that decide; the launchers below launch what they return and
+// xps_gemm_route reports it.  Neither makes a HIP call but the cached CU count.
+struct GemmRoute {
+    int code = XPS_GEMM_ROUTE_REFUSED;
+    int lead_rows = 0;
+    unsigned grid = 0;
+    int vecA = 0, vecB = 0;       // 16-byte loads (bit 0), XPS_FMT_SPLIT4 operand (bit 1)
+    int fmt = 0;                  // bit 0: A is split4, bit 1: B is
+};
+constexpr int tile_code(int mi, bool edge, bool bf, bool pre) {
+    return XPS_GEMM_ROUTE_TILE | (mi == 2 ? XPS_GEMM_ROUTE_TILE_128 : 0) | (edge ? XPS_GEMM_ROUTE_TILE_EDGE : 0) |
+           (bf ? XPS_GEMM_ROUTE_TILE_BF : 0) | (pre ? XPS_GEMM_ROUTE_TILE_PRE : 0);
+}
+inline bool route_is_big(int code) { return code == XPS_GEMM_ROUTE_SKINNY || (code >= XPS_GEMM_ROUTE_BIG && code <= XPS_GEMM_ROUTE_BIG_DMA); }
+// 64- or 128-row tiles (use_small_tiles over `ncols` columns of tiles and a contraction of `ktot`), `nprob` problems side by side
+inline void route_tiles(GemmRoute& r, int M, int N, int ncols, int ktot, int nprob) {
+    const int mi = use_small_tiles(M, ncols, ktot) ? 1 : 2;
+    r.code = tile_code(mi, (M % (64 * mi)) || (N % BN), bf_mode(), bf_mode() && r.fmt);
+    r.grid = cdiv(N, BN) * cdiv(M, 64 * mi) * nprob;
+}
+// 256-tile launch over the whole rounds of tiles: DMA (both operands split4, whole 32-deep stages; same bits; XPS_GEMM_DMA=0:
+// never), 32-deep stages (opt-in, plain operands), else `plain_code`
+inline void route_big(GemmRoute& r, int M, int N, int nprob, bool k32, int plain_code) {
+    r.lead_rows = big_split_rows(M, (N / xps_big::TN) * nprob);
+    r.grid = (r.lead_rows / xps_big::TM) * (N / xps_big::TN) * nprob;
+    r.code = (r.fmt == 3 && k32 && dma_enabled()) ? XPS_GEMM_ROUTE_BIG_DMA
+             : (big_deep_allowed() && k32 && r.fmt == 0)      ? XPS_GEMM_ROUTE_BIG_DEEP : plain_code;
+}
+
+// C = A B (+ A2 B2): A [m][k], B [n][k] (BK) or [k][n].  big_ok = false: the 256-tile family is not available (the launcher could
+// not reserve its LDS block).
+GemmRoute route_gemm(bool BK, const float* A, const RowMap& ra, const float* B, const RowMap& rb, const float* A2, const float* B2,
+                     const RowMap& rc, int M, int N, int K, int K2, bool big_ok) {
+    GemmRoute r;
+    r.lead_rows = M;
+    r.vecA = (int)(map_vec_ok(A, ra) && (!A2 || map_vec_ok(A2, ra)));
+    r.vecB = (int)(map_vec_ok(B, rb) && (!B2 || map_vec_ok(B2, rb)));
+    // XPS_FMT_SPLIT4 operands: bit 1 of the vec flags (refused: the request cannot be served)
+    int fA = split4_flag(A, ra, K), fB = split4_flag(B, rb, BK ? K : N);
+    if (A2 && fA > 0) fA = split4_flag(A2, ra, K2);
+    if (B2 && fB > 0) fB = split4_flag(B2, rb, BK ? K2 : N);
+    if (fA < 0 || fB < 0 || ((fA | fB) && (!bf_mode() || M <= SM_MAXM))) return r;
+    r.vecA |= fA; r.vecB |= fB;
+    r.fmt = (fA ? 1 : 0) | (fB ? 2 : 0);
+    const bool k32 = K % 32 == 0 && K2 % 32 == 0;
+    const bool big = big_ok && big_enabled() && M % xps_big::TM == 0 && rc.rpg >= M && big_plain(A, ra, M) && big_plain(B, rb, BK ? N : K) &&
+                     (!A2 || (big_plain(A2, ra, M) && big_plain(B2, rb, BK ? N : K2)));
+    if (M <= SM_MAXM) {
+        r.code = XPS_GEMM_ROUTE_SMALL_M;
+        r.grid = cdiv(N, 64);
+    } else if (big && !BK && dma_enabled() && r.fmt == 3 && N < xps_big::TN && N % 4 == 0 && rb.ld >= xps_big::TN && M / xps_big::TM >= 96 &&
+               k32 && K + K2 >= 512) {
+        // skinny input gradient (configs[3] layer 0: 40960 x 100 x 3072, HBM-bound on A): ONE 256-wide tile per 256 rows on the
+        // LDS-DMA loop; needs B's rows readable (and split4) to 256 columns: the caller hands a zero-padded image (rb.ld >= 256)
+        r.code = XPS_GEMM_ROUTE_SKINNY;
+        r.grid = M / xps_big::TM;
+    } else if (big && N % xps_big::TN == 0 && K % BKT == 0 && K2 % BKT == 0 && K >= 64 &&
+               (long long)(M / xps_big::TM) * (N / xps_big::TN) >= big_min_tiles()) {
+        route_big(r, M, N, 1, k32, XPS_GEMM_ROUTE_BIG + r.fmt);
+    } else {
+        route_tiles(r, M, N, N, K + K2, 1);
+    }
+    return r;
+}
+
+// nprob products C_i = A B_i^T sharing A, the sizes and the row maps
+GemmRoute route_gemm_multi(const float* A, const RowMap& ra, const float* const* B, const RowMap& rb, const RowMap& rc, int nprob,
+                           int M, int N, int K, bool big_ok) {
+    GemmRoute r;
+    r.lead_rows = M;
+    bool vb = true;
+    int fA = split4_flag(A, ra, K), fB = 0;
+    for (int i = 0; i < nprob; ++i) vb = vb && map_vec_ok(B[i], rb);
+    for (int i = 0; i < nprob && fB >= 0; ++i) fB = split4_flag(B[i], rb, K);
+    if (fA < 0 || fB < 0 || ((fA | fB) && !bf_mode())) return r;
+    r.vecA = (int)map_vec_ok(A, ra) | fA; r.vecB = (int)vb | fB;
+    r.fmt = (fA ? 1 : 0) | (fB ? 2 : 0);
+    // weight-stationary projection: small K (the weights of a 256-column slice fit the registers of a block), many rows
+    if (bf_mode() && proj_ws_enabled() && K >= 32 && K <= 256 && K % 4 == 0 && N % 32 == 0 && (long long)nprob * N >= 256 && M >= 4096 &&
+        r.vecA && vb && ra.rpg >= M && rb.rpg >= N && rc.rpg >= M) {
+        const int S = cdiv((long long)nprob * N, 256), tiles = cdiv(M, 64), cus = device_cus();      // one persistent block per CU
+        const int grid = ((cus < tiles * S ? cus : tiles * S) / S) * S;                              // every row group has all its slices
+        if (grid >= S) {
+            r.code = XPS_GEMM_ROUTE_PROJ_WS + 2 * ((K + 31) / 32);
+            r.grid = grid;
+            return r;
+        }
+    }
+    if (big_ok && big_enabled() && M % xps_big::TM == 0 && N % xps_big::TN == 0 && K % BKT == 0 && K >= 64 && vb &&
+        (long long)(M / xps_big::TM) * (N / xps_big::TN) * nprob >= big_min_tiles() && big_plain(A, ra, M) && rb.rpg >= N && rc.rpg >= M)
+        route_big(r, M, N, nprob, K % 32 == 0, XPS_GEMM_ROUTE_BIG);
+    else
+        route_tiles(r, M, N, N * nprob, K, nprob);
+    return r;
+}
+
+// ---- the launchers: route, then one switch that launches -----------------------------------------------------------------------
+// they return 0, -1 (a launch failed), -2 (refused: an XPS_FMT_SPLIT4 operand that cannot be served) or -3 (no LDS for proj_ws)
+#define XPS_TILE_CASES(LAUNCH, MI_, EDGE_)                                     \
+    case tile_code(MI_, EDGE_, false, false): LAUNCH(MI_, EDGE_, false, false); break; \
+    case tile_code(MI_, EDGE_, true, false): LAUNCH(MI_, EDGE_, true, false); break;   \
+    case tile_code(MI_, EDGE_, true, true): LAUNCH(MI_, EDGE_, true, true); break
+#define XPS_ALL_TILE_CASES(LAUNCH) \
+    XPS_TILE_CASES(LAUNCH, 1, false); XPS_TILE_CASES(LAUNCH, 1, true); XPS_TILE_CASES(LAUNCH, 2, false); XPS_TILE_CASES(LAUNCH, 2, true)
+
+template <bool BK>
+bool big_ready() {          // once per form: allow the 96- / 144-KB dynamic LDS blocks (the skinny kernel belongs to nn / nn2)
+    static const bool ready =
+        big_prepare(gemm_big_kernel<true, BK, false, 0>, BIG_LDS) && big_prepare(gemm_big_kernel<true, BK, false, 1>, BIG_LDS) &&
+        big_prepare(gemm_big_kernel<true, BK, false, 2>, BIG_LDS) && big_prepare(gemm_big_kernel<true, BK, false, 3>, BIG_LDS) &&
+        big_prepare(gemm_big_kernel<true, BK, true>, BIG_LDS32) && big_prepare(gemm_big_kernel<true, BK, false, 4>, xps_big::direct_dma_lds<!BK>()) &&
+        (BK || big_prepare(gemm_big_kernel<true, false, false, 5>, xps_big::direct_dma_lds<true>()));
+    return ready;
+}
+
+template <bool BK>
 int launch_gemm(const float* A, const RowMap& ra, const float* B, const RowMap& rb, const float* A2, const float* B2, int K2,
                 float* C, const RowMap& rc, const float* bias, int M, int N, int K, int accumulate, hipStream_t st) {
     const int kchunk = ((K + BKT - 1) / BKT) * BKT + BKT;
-    int vecA = (int)(map_vec_ok(A, ra) && (!A2 || map_vec_ok(A2, ra)));
-    int vecB = (int)(map_vec_ok(B, rb) && (!B2 || map_vec_ok(B2, rb)));
-    // XPS_FMT_SPLIT4 operands: bit 1 of the vec flags (-2: the request cannot be served)
-    int fA = split4_flag(A, ra, AK ? K : M), fB = split4_flag(B, rb, BK ? K : N);
-    if (A2 && fA > 0) fA = split4_flag(A2, ra, AK ? K2 : M);
-    if (B2 && fB > 0) fB = split4_flag(B2, rb, BK ? K2 : N);
-    if (fA < 0 || fB < 0 || ((fA | fB) && (!bf_mode() || M <= SM_MAXM))) return -2;
-    vecA |= fA; vecB |= fB;
-    const int fmt = (fA ? 1 : 0) | (fB ? 2 : 0);
-    if (M <= SM_MAXM) {
-        hipLaunchKernelGGL((gemm_small_kernel<AK, BK>), dim3(cdiv(N, 64)), dim3(1024), 0, st, A, ra, B, rb, A2, B2, K2, C, rc,
-                           bias, M, N, K, accumulate, vecB);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    if constexpr (AK && !BK) {
-        // skinny input gradient (configs[3] layer 0: 40960 x 100 x 3072, HBM-bound on A): ONE 256-wide tile per 256 rows on the
-        // LDS-DMA loop; needs B's rows readable (and split4) to 256 columns: the caller hands a zero-padded image (rb.ld >= 256)
-        if (big_enabled() && dma_enabled() && fmt == 3 && N < xps_big::TN && N % 4 == 0 && rb.ld >= xps_big::TN && M % xps_big::TM == 0 &&
-            M / xps_big::TM >= 96 && K % 32 == 0 && K2 % 32 == 0 && K + K2 >= 512 && big_plain(A, ra, M) && big_plain(B, rb, K) &&
-            (!A2 || (big_plain(A2, ra, M) && big_plain(B2, rb, K2))) && rc.rpg >= M) {
-            constexpr int lds = xps_big::direct_dma_lds<true>();
-            static const bool ready5 = big_prepare(gemm_big_kernel<true, false, false, 5>, lds);
-            if (ready5) {
-                hipLaunchKernelGGL((gemm_big_kernel<true, false, false, 5>), dim3(M / xps_big::TM), dim3(xps_big::NTHR), lds, st,
-                                   A, ra.ld, B, rb.ld, A2, B2, K2, C, rc.ld, bias, N, K, accumulate, fmt);
-                return hipGetLastError() == hipSuccess ? 0 : -1;
-            }
+    while (M > 0) {
+        GemmRoute r = route_gemm(BK, A, ra, B, rb, A2, B2, rc, M, N, K, K2, true);
+        if (route_is_big(r.code) && !big_ready<BK>()) r = route_gemm(BK, A, ra, B, rb, A2, B2, rc, M, N, K, K2, false);
+        const dim3 grid(r.grid);
+#define XPS_BIG_CASE(CODE_, DEEP_, FMT_, LDS_)                                                                              \
+    case CODE_:                                                                                                             \
+        if constexpr (FMT_ != 5 || !BK) /* (the skinny kernel exists for nn / nn2 only) */                                  \
+            hipLaunchKernelGGL((gemm_big_kernel<true, BK, DEEP_, FMT_>), grid, dim3(xps_big::NTHR), LDS_, st, A, ra.ld, B, rb.ld, A2, B2, K2, \
+                           C, rc.ld, bias, N, K, accumulate, r.fmt);                                                     \
+        break
+#define XPS_LAUNCH_TILE(MI_, EDGE_, BF_, PRE_)                                                                               \
+    hipLaunchKernelGGL((gemm_f32_kernel<true, BK, MI_, EDGE_, BF_, PRE_>), grid, dim3(256), 0, st, A, ra, B, rb, A2, B2, K2, C, rc,  \
+                       bias, M, N, K, kchunk, 0LL, accumulate, r.vecA, r.vecB)
+        switch (r.code) {
+            case XPS_GEMM_ROUTE_REFUSED: return -2;
+            case XPS_GEMM_ROUTE_SMALL_M:
+                hipLaunchKernelGGL((gemm_small_kernel<true, BK>), grid, dim3(1024), 0, st, A, ra, B, rb, A2, B2, K2, C, rc, bias, M, N, K,
+                                   accumulate, r.vecB);
+                break;
+            XPS_BIG_CASE(XPS_GEMM_ROUTE_BIG + 0, false, 0, BIG_LDS); XPS_BIG_CASE(XPS_GEMM_ROUTE_BIG + 1, false, 1, BIG_LDS);
+            XPS_BIG_CASE(XPS_GEMM_ROUTE_BIG + 2, false, 2, BIG_LDS); XPS_BIG_CASE(XPS_GEMM_ROUTE_BIG + 3, false, 3, BIG_LDS);
+            XPS_BIG_CASE(XPS_GEMM_ROUTE_BIG_DEEP, true, 0, BIG_LDS32);
+            XPS_BIG_CASE(XPS_GEMM_ROUTE_BIG_DMA, false, 4, xps_big::direct_dma_lds<!BK>());
+            XPS_BIG_CASE(XPS_GEMM_ROUTE_SKINNY, false, 5, xps_big::direct_dma_lds<true>());
+            XPS_ALL_TILE_CASES(XPS_LAUNCH_TILE);
+            default: return -1;
         }
+#undef XPS_BIG_CASE
+#undef XPS_LAUNCH_TILE
+        if (hipGetLastError() != hipSuccess) return -1;
+        // the rows behind the whole rounds (only a 256-tile launch leaves any: plain operands, so a row is ld floats)
+        A += (long long)r.lead_rows * ra.ld;
+        if (A2) A2 += (long long)r.lead_rows * ra.ld;
+        C += (long long)r.lead_rows * rc.ld;
+        M -= r.lead_rows;
     }
-    if (big_enabled() && M % xps_big::TM == 0 && N % xps_big::TN == 0 && K % BKT == 0 && K2 % BKT == 0 && K >= 64 &&
-        (long long)(M / xps_big::TM) * (N / xps_big::TN) >= big_min_tiles() &&
-        big_plain(A, ra, AK ? M : K) && big_plain(B, rb, BK ? N : K) && (!A2 || (big_plain(A2, ra, AK ? M : K2) && big_plain(B2, rb, BK ? N : K2))) &&
-        rc.rpg >= M) {
-        static const bool ready = big_prepare(gemm_big_kernel<AK, BK, false, 0>, BIG_LDS) && big_prepare(gemm_big_kernel<AK, BK, false, 1>, BIG_LDS) &&
-                                  big_prepare(gemm_big_kernel<AK, BK, false, 2>, BIG_LDS) && big_prepare(gemm_big_kernel<AK, BK, false, 3>, BIG_LDS) &&
-                                  big_prepare(gemm_big_kernel<AK, BK, true>, BIG_LDS32);
-        if (ready) {
-            const int Mfull = M;
-            M = big_split_rows(M, N / xps_big::TN);
-            const dim3 bgrid((M / xps_big::TM) * (N / xps_big::TN));
-            // the rows behind the whole rounds: 128-tile kernels (the recursion ends there: too few tiles for another 256-tile launch)
-            const int Mtail = Mfull - M;
-            auto run_tail = [&]() -> int {
-                if (Mtail <= 0) return 0;
-                const float* At = AK ? A + (long long)M * ra.ld : A + M;
-                const float* A2t = A2 ? (AK ? A2 + (long long)M * ra.ld : A2 + M) : nullptr;
-                return launch_gemm<AK, BK>(At, ra, B, rb, A2t, B2, K2, C + (long long)M * rc.ld, rc, bias, Mtail, N, K, accumulate, st);
-            };
-            bool dma_done = false;
-            if constexpr (AK) {
-                // both operands split4, A stored [m][k], whole 32-deep stages: the LDS-DMA k loop (same bits; XPS_GEMM_DMA=0: never)
-                if (fmt == 3 && K % 32 == 0 && K2 % 32 == 0 && dma_enabled()) {
-                    constexpr int lds = xps_big::direct_dma_lds<!BK>();
-                    static const bool ready4 = big_prepare(gemm_big_kernel<AK, BK, false, 4>, lds);
-                    if (ready4) {
-                        hipLaunchKernelGGL((gemm_big_kernel<AK, BK, false, 4>), bgrid, dim3(xps_big::NTHR), lds, st,
-                                           A, ra.ld, B, rb.ld, A2, B2, K2, C, rc.ld, bias, N, K, accumulate, fmt);
-                        dma_done = true;
-                    }
-                }
-            }
-            if (dma_done) {
-            } else if (big_deep_allowed() && K % 32 == 0 && K2 % 32 == 0 && fmt == 0)
-                hipLaunchKernelGGL((gemm_big_kernel<AK, BK, true>), bgrid, dim3(xps_big::NTHR), BIG_LDS32, st,
-                                   A, ra.ld, B, rb.ld, A2, B2, K2, C, rc.ld, bias, N, K, accumulate, fmt);
-            else if (fmt == 0)
-                hipLaunchKernelGGL((gemm_big_kernel<AK, BK, false, 0>), bgrid, dim3(xps_big::NTHR), BIG_LDS, st,
-                                   A, ra.ld, B, rb.ld, A2, B2, K2, C, rc.ld, bias, N, K, accumulate, fmt);
-            else if (fmt == 1)
-                hipLaunchKernelGGL((gemm_big_kernel<AK, BK, false, 1>), bgrid, dim3(xps_big::NTHR), BIG_LDS, st,
-                                   A, ra.ld, B, rb.ld, A2, B2, K2, C, rc.ld, bias, N, K, accumulate, fmt);
-            else if (fmt == 2)
-                hipLaunchKernelGGL((gemm_big_kernel<AK, BK, false, 2>), bgrid, dim3(xps_big::NTHR), BIG_LDS, st,
-                                   A, ra.ld, B, rb.ld, A2, B2, K2, C, rc.ld, bias, N, K, accumulate, fmt);
-            else
-                hipLaunchKernelGGL((gemm_big_kernel<AK, BK, false, 3>), bgrid, dim3(xps_big::NTHR), BIG_LDS, st,
-                                   A, ra.ld, B, rb.ld, A2, B2, K2, C, rc.ld, bias, N, K, accumulate, fmt);
-            if (hipGetLastError() != hipSuccess) return -1;
-            return run_tail();
+    return 0;
+}
+
+int launch_gemm_multi(const float* A, const RowMap& ra, const float* const* B, const RowMap& rb, float* const* C, const RowMap& rc,
+                      const float* const* bias, int nprob, int M, int N, int K, hipStream_t st) {
+    NtMulti pm;
+    for (int i = 0; i < 4; ++i) {
+        const int j = i < nprob ? i : 0;
+        pm.B[i] = B[j]; pm.C[i] = C[j]; pm.bias[i] = bias ? bias[j] : nullptr;
+    }
+    auto big_ready = [] {          // once: allow the 96- / 144-KB dynamic LDS blocks
+        static const bool ready = big_prepare(gemm_big_nt_multi_kernel<false>, BIG_LDS) && big_prepare(gemm_big_nt_multi_kernel<true>, BIG_LDS32) &&
+                                  big_prepare(gemm_big_nt_multi_kernel<false, true>, xps_big::direct_dma_lds<false>());
+        return ready;
+    };
+    while (M > 0) {
+        GemmRoute r = route_gemm_multi(A, ra, B, rb, rc, nprob, M, N, K, true);
+        if (route_is_big(r.code) && !big_ready()) r = route_gemm_multi(A, ra, B, rb, rc, nprob, M, N, K, false);
+        const dim3 grid(r.grid);
+#define XPS_WS_CASE(KT_)                                                                                                  \
+    case XPS_GEMM_ROUTE_PROJ_WS + KT_: {                                                                                  \
+        static const bool ok_ = big_prepare(proj_ws_kernel<KT_>, proj_ws_lds(KT_));                                        \
+        if (!ok_) return -3;                                                                                              \
+        hipLaunchKernelGGL(proj_ws_kernel<KT_>, grid, dim3(512), proj_ws_lds(KT_), st, A, ra.ld, pm, rb.ld, rc.ld, M, N, K, nprob, \
+                           r.fmt & 1, r.fmt >> 1);                                                                        \
+    } break
+#define XPS_LAUNCH_BIGM(DEEP_, DMA_, LDS_)                                                                                \
+    hipLaunchKernelGGL((gemm_big_nt_multi_kernel<DEEP_, DMA_>), grid, dim3(xps_big::NTHR), LDS_, st, A, ra.ld, pm, rb.ld, rc.ld, N, K, \
+                       nprob, r.fmt)
+#define XPS_LAUNCH_NTM(MI_, EDGE_, BF_, PRE_)                                                                             \
+    hipLaunchKernelGGL((gemm_nt_multi_kernel<MI_, EDGE_, BF_, PRE_>), grid, dim3(256), 0, st, A, ra, pm, rb, rc, M, N, K, nprob, \
+                       r.vecA, r.vecB)
+        switch (r.code) {
+            case XPS_GEMM_ROUTE_REFUSED: return -2;
+            XPS_WS_CASE(2); XPS_WS_CASE(4); XPS_WS_CASE(6); XPS_WS_CASE(8); XPS_WS_CASE(10); XPS_WS_CASE(12); XPS_WS_CASE(14); XPS_WS_CASE(16);
+            case XPS_GEMM_ROUTE_BIG: XPS_LAUNCH_BIGM(false, false, BIG_LDS); break;
+            case XPS_GEMM_ROUTE_BIG_DEEP: XPS_LAUNCH_BIGM(true, false, BIG_LDS32); break;
+            case XPS_GEMM_ROUTE_BIG_DMA: XPS_LAUNCH_BIGM(false, true, xps_big::direct_dma_lds<false>()); break;
+            XPS_ALL_TILE_CASES(XPS_LAUNCH_NTM);
+            default: return -1;
         }
+#undef XPS_WS_CASE
+#undef XPS_LAUNCH_BIGM
+#undef XPS_LAUNCH_NTM
+        if (hipGetLastError() != hipSuccess) return -1;
+        A += (long long)r.lead_rows * ra.ld;                     // (see launch_gemm)
+        for (int i = 0; i < 4; ++i) pm.C[i] += (long long)r.lead_rows * rc.ld;
+        M -= r.lead_rows;
     }
-#define XPS_LAUNCH_GEMM(MI_, EDGE_, BF_)                                                                              \
-    do {                                                                                                              \
-        if (BF_ && fmt)                                                                                               \
-            hipLaunchKernelGGL((gemm_f32_kernel<AK, BK, MI_, EDGE_, BF_, BF_>), grid, dim3(256), 0, st, A, ra, B, rb, A2, B2, K2, C, rc, \
-                               bias, M, N, K, kchunk, 0LL, accumulate, vecA, vecB);                                   \
-        else                                                                                                          \
-            hipLaunchKernelGGL((gemm_f32_kernel<AK, BK, MI_, EDGE_, BF_>), grid, dim3(256), 0, st, A, ra, B, rb, A2, B2, K2, C, rc, \
-                               bias, M, N, K, kchunk, 0LL, accumulate, vecA, vecB);                                   \
-    } while (0)
-    const bool bf = bf_mode();
-    if (use_small_tiles(M, N, K + K2)) {
-        dim3 grid(cdiv(N, BN) * cdiv(M, 64));
-        const bool edge = (M % 64) || (N % BN);
-        if (bf) { if (edge) XPS_LAUNCH_GEMM(1, true, true); else XPS_LAUNCH_GEMM(1, false, true); }
-        else { if (edge) XPS_LAUNCH_GEMM(1, true, false); else XPS_LAUNCH_GEMM(1, false, false); }
-    } else {
-        dim3 grid(cdiv(N, BN) * cdiv(M, 128));
-        const bool edge = (M % 128) || (N % BN);
-        if (bf) { if (edge) XPS_LAUNCH_GEMM(2, true, true); else XPS_LAUNCH_GEMM(2, false, true); }
-        else { if (edge) XPS_LAUNCH_GEMM(2, true, false); else XPS_LAUNCH_GEMM(2, false, false); }
+    return 0;
+}
+#undef XPS_TILE_CASES
+#undef XPS_ALL_TILE_CASES
+
+// a launcher's return code as the entry point's
+int gemm_status(const char* entry, int lrc) {
+    if (lrc == 0) return XPS_OK;
+    if (lrc == -2) {
+        xps_set_error("%s: XPS_FMT_SPLIT4 operand needs bf16x3 mode, 16-byte aligned rows and a contiguous extent that is a multiple of 4 "
+                      "(nt / nn / nn2: and M > 16)", entry);
+        return XPS_E_INVALID;
     }
-#undef XPS_LAUNCH_GEMM
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    if (lrc == -3) xps_set_error("%s: cannot reserve the LDS block of the projection kernel", entry);
+    else xps_set_error("%s: launch failed: %s", entry, hipGetErrorString(hipGetLastError()));
+    return XPS_E_HIP;
 }
 }  // namespace
 
@@ -919,17 +1034,8 @@ extern "C" int xps_gemm_nt_f32(const float* A, const xps_rowmap* ra_, const floa
     XPS_CHECK_ARG(A && B && C && ra_ && rb_ && rc_, "null argument");
     XPS_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "negative size");
     if (M == 0 || N == 0) return XPS_OK;
-    RowMap ra = to_rowmap(ra_), rb = to_rowmap(rb_), rc = to_rowmap(rc_);
-    const int lrc = launch_gemm<true, true>(A, ra, B, rb, nullptr, nullptr, 0, C, rc, bias, M, N, K, accumulate, (hipStream_t)stream);
-    if (lrc == -2) {
-        xps_set_error("xps_gemm_nt_f32: XPS_FMT_SPLIT4 operand needs bf16x3 mode, M > 16, 16-byte aligned rows and a contiguous extent that is a multiple of 4");
-        return XPS_E_INVALID;
-    }
-    if (lrc) {
-        xps_set_error("xps_gemm_nt_f32: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return XPS_E_HIP;
-    }
-    return XPS_OK;
+    return gemm_status(__func__, launch_gemm<true>(A, to_rowmap(ra_), B, to_rowmap(rb_), nullptr, nullptr, 0, C, to_rowmap(rc_), bias,
+                                                   M, N, K, accumulate, (hipStream_t)stream));
 }
 
 extern "C" int xps_gemm_nn_f32(const float* A, const xps_rowmap* ra_, const float* B, const xps_rowmap* rb_,
@@ -938,17 +1044,18 @@ extern "C" int xps_gemm_nn_f32(const float* A, const xps_rowmap* ra_, const floa
     XPS_CHECK_ARG(A && B && C && ra_ && rb_ && rc_, "null argument");
     XPS_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "negative size");
     if (M == 0 || N == 0) return XPS_OK;
-    RowMap ra = to_rowmap(ra_), rb = to_rowmap(rb_), rc = to_rowmap(rc_);
-    const int lrc = launch_gemm<true, false>(A, ra, B, rb, nullptr, nullptr, 0, C, rc, nullptr, M, N, K, accumulate, (hipStream_t)stream);
-    if (lrc == -2) {
-        xps_set_error("xps_gemm_nn_f32: XPS_FMT_SPLIT4 operand needs bf16x3 mode, M > 16, 16-byte aligned rows and a contiguous extent that is a multiple of 4");
-        return XPS_E_INVALID;
-    }
-    if (lrc) {
-        xps_set_error("xps_gemm_nn_f32: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return XPS_E_HIP;
-    }
-    return XPS_OK;
+    return gemm_status(__func__, launch_gemm<false>(A, to_rowmap(ra_), B, to_rowmap(rb_), nullptr, nullptr, 0, C, to_rowmap(rc_), nullptr,
+                                                    M, N, K, accumulate, (hipStream_t)stream));
+}
+
+extern "C" int xps_gemm_nn2_f32(const float* A1, const float* B1, int K1, const float* A2, const float* B2, int K2,
+                                const xps_rowmap* ra_, const xps_rowmap* rb_, float* C, const xps_rowmap* rc_,
+                                int M, int N, int accumulate, void* stream) {
+    XPS_CHECK_ARG(A1 && B1 && A2 && B2 && C && ra_ && rb_ && rc_, "null argument");
+    XPS_CHECK_ARG(M >= 0 && N >= 0 && K1 >= 0 && K2 >= 0, "negative size");
+    if (M == 0 || N == 0) return XPS_OK;
+    return gemm_status(__func__, launch_gemm<false>(A1, to_rowmap(ra_), B1, to_rowmap(rb_), A2, B2, K2, C, to_rowmap(rc_), nullptr,
+                                                    M, N, K1, accumulate, (hipStream_t)stream));
 }
 
 extern "C" int xps_gemm_nt_multi_f32(const float* A, const xps_rowmap* ra_, const float* const* B, const xps_rowmap* rb_,
@@ -958,128 +1065,35 @@ extern "C" int xps_gemm_nt_multi_f32(const float* A, const xps_rowmap* ra_, cons
     XPS_CHECK_ARG(nprob >= 1 && nprob <= 4, "1..4 problems");
     XPS_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "negative size");
     if (M == 0 || N == 0) return XPS_OK;
-    RowMap ra = to_rowmap(ra_), rb = to_rowmap(rb_), rc = to_rowmap(rc_);
-    NtMulti pm;
-    bool vb = true;
-    for (int i = 0; i < 4; ++i) {
-        const int j = i < nprob ? i : 0;
-        XPS_CHECK_ARG(B[j] && C[j], "null problem pointer");
-        pm.B[i] = B[j]; pm.C[i] = C[j]; pm.bias[i] = bias ? bias[j] : nullptr;
-        vb = vb && map_vec_ok(B[j], rb);
-    }
-    int vecA = (int)map_vec_ok(A, ra), vecB = (int)vb;
-    int fA = split4_flag(A, ra, K), fB = 0;
-    for (int i = 0; i < nprob && fB >= 0; ++i) fB = split4_flag(B[i], rb, K);
-    if (fA < 0 || fB < 0 || ((fA | fB) && !bf_mode())) {
-        xps_set_error("xps_gemm_nt_multi_f32: XPS_FMT_SPLIT4 operand needs bf16x3 mode, 16-byte aligned rows and K %% 4 == 0");
-        return XPS_E_INVALID;
-    }
-    vecA |= fA; vecB |= fB;
-    const int fmt = (fA ? 1 : 0) | (fB ? 2 : 0);
-    // weight-stationary projection: small K (the weights of a 256-column slice fit the registers of a block), many rows
-    if (bf_mode() && proj_ws_enabled() && K >= 32 && K <= 256 && K % 4 == 0 && N % 32 == 0 && (long long)nprob * N >= 256 && M >= 4096 &&
-        vecA && vb && ra.rpg >= M && rb.rpg >= N && rc.rpg >= M) {
-        const int KT = 2 * ((K + 31) / 32);
-        static const int cus = [] {                          // one persistent block per CU
-            int dev = 0, n = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) return n;
-            return 256;
-        }();
-        const int S = cdiv((long long)nprob * N, 256), tiles = cdiv(M, 64);
-        int grid = cus < tiles * S ? cus : tiles * S;
-        grid = (grid / S) * S;                              // every row group has all its slices
-        if (grid >= S) {
-#define XPS_LAUNCH_WS(KT_)                                                                                                            \
-    do {                                                                                                                              \
-        static const bool ok_ = big_prepare(proj_ws_kernel<KT_>, proj_ws_lds(KT_));                                                    \
-        if (!ok_) { xps_set_error("xps_gemm_nt_multi_f32: cannot reserve %d bytes of LDS", proj_ws_lds(KT_)); return XPS_E_HIP; }       \
-        hipLaunchKernelGGL(proj_ws_kernel<KT_>, dim3(grid), dim3(512), proj_ws_lds(KT_), (hipStream_t)stream, A, ra.ld, pm, rb.ld, rc.ld, \
-                           M, N, K, nprob, fA ? 1 : 0, fB ? 1 : 0);                                                                      \
-    } while (0)
-            switch (KT) {
-                case 2: XPS_LAUNCH_WS(2); break;
-                case 4: XPS_LAUNCH_WS(4); break;
-                case 6: XPS_LAUNCH_WS(6); break;
-                case 8: XPS_LAUNCH_WS(8); break;
-                case 10: XPS_LAUNCH_WS(10); break;
-                case 12: XPS_LAUNCH_WS(12); break;
-                case 14: XPS_LAUNCH_WS(14); break;
-                default: XPS_LAUNCH_WS(16); break;
-            }
-#undef XPS_LAUNCH_WS
-            XPS_CHECK_LAUNCH();
-            return XPS_OK;
-        }
-    }
-    if (big_enabled() && M % xps_big::TM == 0 && N % xps_big::TN == 0 && K % BKT == 0 && K >= 64 && vb &&
-        (long long)(M / xps_big::TM) * (N / xps_big::TN) * nprob >= big_min_tiles() &&
-        big_plain(A, ra, M) && rb.rpg >= N && rc.rpg >= M) {
-        static const bool ready = big_prepare(gemm_big_nt_multi_kernel<false>, BIG_LDS) && big_prepare(gemm_big_nt_multi_kernel<true>, BIG_LDS32);
-        if (ready) {
-            const int Mfull = M;
-            M = big_split_rows(M, (N / xps_big::TN) * nprob);
-            const dim3 bgrid((M / xps_big::TM) * (N / xps_big::TN) * nprob);
-            static const bool ready_dma = big_prepare(gemm_big_nt_multi_kernel<false, true>, xps_big::direct_dma_lds<false>());
-            if (fmt == 3 && K % 32 == 0 && dma_enabled() && ready_dma)          // both operands split4: the LDS-DMA k loop (same bits)
-                hipLaunchKernelGGL((gemm_big_nt_multi_kernel<false, true>), bgrid, dim3(xps_big::NTHR), xps_big::direct_dma_lds<false>(),
-                                   (hipStream_t)stream, A, ra.ld, pm, rb.ld, rc.ld, N, K, nprob, fmt);
-            else if (big_deep_allowed() && K % 32 == 0 && fmt == 0)
-                hipLaunchKernelGGL(gemm_big_nt_multi_kernel<true>, bgrid, dim3(xps_big::NTHR), BIG_LDS32, (hipStream_t)stream, A, ra.ld, pm,
-                                   rb.ld, rc.ld, N, K, nprob, fmt);
-            else
-                hipLaunchKernelGGL(gemm_big_nt_multi_kernel<false>, bgrid, dim3(xps_big::NTHR), BIG_LDS,
-                               (hipStream_t)stream, A, ra.ld, pm, rb.ld, rc.ld, N, K, nprob, fmt);
-            XPS_CHECK_LAUNCH();
-            if (Mfull > M) {
-                // the rows behind the whole rounds: the 128-tile kernels (see big_split_rows)
-                float* Ct[4];
-                for (int i = 0; i < nprob; ++i) Ct[i] = C[i] + (long long)M * rc.ld;
-                return xps_gemm_nt_multi_f32(A + (long long)M * ra.ld, ra_, B, rb_, Ct, rc_, bias, nprob, Mfull - M, N, K, stream);
-            }
-            return XPS_OK;
-        }
-    }
-#define XPS_LAUNCH_NTM(MI_, EDGE_, BF_)                                                                                  \
-    do {                                                                                                                 \
-        if (BF_ && fmt)                                                                                                  \
-            hipLaunchKernelGGL((gemm_nt_multi_kernel<MI_, EDGE_, BF_, BF_>), dim3(cdiv(N, BN) * cdiv(M, 64 * MI_) * nprob), dim3(256), 0, \
-                               (hipStream_t)stream, A, ra, pm, rb, rc, M, N, K, nprob, vecA, vecB);                        \
-        else                                                                                                             \
-            hipLaunchKernelGGL((gemm_nt_multi_kernel<MI_, EDGE_, BF_>), dim3(cdiv(N, BN) * cdiv(M, 64 * MI_) * nprob), dim3(256), 0,    \
-                               (hipStream_t)stream, A, ra, pm, rb, rc, M, N, K, nprob, vecA, vecB);                        \
-    } while (0)
-    const bool bf = bf_mode();
-    if (use_small_tiles(M, N * nprob, K)) {
-        const bool edge = (M % 64) || (N % BN);
-        if (bf) { if (edge) XPS_LAUNCH_NTM(1, true, true); else XPS_LAUNCH_NTM(1, false, true); }
-        else { if (edge) XPS_LAUNCH_NTM(1, true, false); else XPS_LAUNCH_NTM(1, false, false); }
-    } else {
-        const bool edge = (M % 128) || (N % BN);
-        if (bf) { if (edge) XPS_LAUNCH_NTM(2, true, true); else XPS_LAUNCH_NTM(2, false, true); }
-        else { if (edge) XPS_LAUNCH_NTM(2, true, false); else XPS_LAUNCH_NTM(2, false, false); }
-    }
-#undef XPS_LAUNCH_NTM
-    XPS_CHECK_LAUNCH();
-    return XPS_OK;
+    for (int i = 0; i < nprob; ++i) XPS_CHECK_ARG(B[i] && C[i], "null problem pointer");
+    return gemm_status(__func__, launch_gemm_multi(A, to_rowmap(ra_), B, to_rowmap(rb_), C, to_rowmap(rc_), bias, nprob, M, N, K,
+                                                   (hipStream_t)stream));
 }
 
-extern "C" int xps_gemm_nn2_f32(const float* A1, const float* B1, int K1, const float* A2, const float* B2, int K2,
-                                const xps_rowmap* ra_, const xps_rowmap* rb_, float* C, const xps_rowmap* rc_,
-                                int M, int N, int accumulate, void* stream) {
-    XPS_CHECK_ARG(A1 && B1 && A2 && B2 && C && ra_ && rb_ && rc_, "null argument");
-    XPS_CHECK_ARG(M >= 0 && N >= 0 && K1 >= 0 && K2 >= 0, "negative size");
-    if (M == 0 || N == 0) return XPS_OK;
-    RowMap ra = to_rowmap(ra_), rb = to_rowmap(rb_), rc = to_rowmap(rc_);
-    const int lrc = launch_gemm<true, false>(A1, ra, B1, rb, A2, B2, K2, C, rc, nullptr, M, N, K1, accumulate, (hipStream_t)stream);
-    if (lrc == -2) {
-        xps_set_error("xps_gemm_nn2_f32: XPS_FMT_SPLIT4 operand needs bf16x3 mode, M > 16, 16-byte aligned rows and a contiguous extent that is a multiple of 4");
-        return XPS_E_INVALID;
-    }
-    if (lrc) {
-        xps_set_error("xps_gemm_nn2_f32: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return XPS_E_HIP;
-    }
-    return XPS_OK;
+// what the launchers above would launch (xps.h)
+extern "C" int xps_gemm_route(int form, const float* A, const xps_rowmap* ra_, const void* B, const xps_rowmap* rb_, const float* A2,
+                              const float* B2, const xps_rowmap* rc_, int M, int N, int K, int K2, int nprob, int* lead_rows,
+                              int* tail_route) {
+    if (lead_rows) *lead_rows = 0;
+    if (tail_route) *tail_route = XPS_GEMM_ROUTE_NONE;
+    const bool multi = form == XPS_GEMM_FORM_NT_MULTI, two = form == XPS_GEMM_FORM_NN2;
+    if (form < XPS_GEMM_FORM_NT || form > XPS_GEMM_FORM_NT_MULTI || !A || !B || !ra_ || !rb_ || !rc_ || (two && (!A2 || !B2)) ||
+        M < 0 || N < 0 || K < 0 || (two && K2 < 0) || (multi && (nprob < 1 || nprob > 4)))
+        return XPS_GEMM_ROUTE_REFUSED;
+    if (M == 0 || N == 0) return XPS_GEMM_ROUTE_NONE;
+    if (!two) { A2 = B2 = nullptr; K2 = 0; }
+    const RowMap ra = to_rowmap(ra_), rb = to_rowmap(rb_), rc = to_rowmap(rc_);
+    const bool BK = form == XPS_GEMM_FORM_NT;
+    auto route = [&](int row0) {
+        const float* Ar = A + (long long)row0 * ra.ld;
+        return multi ? route_gemm_multi(Ar, ra, static_cast<const float* const*>(B), rb, rc, nprob, M - row0, N, K, true)
+                     : route_gemm(BK, Ar, ra, static_cast<const float*>(B), rb, A2 ? A2 + (long long)row0 * ra.ld : nullptr, B2, rc,
+                                  M - row0, N, K, K2, true);
+    };
+    const GemmRoute r = route(0);
+    if (lead_rows) *lead_rows = r.lead_rows;
+    if (tail_route && r.code != XPS_GEMM_ROUTE_REFUSED && r.lead_rows < M) *tail_route = route(r.lead_rows).code;
+    return r.code;
 }
 
 extern "C" size_t xps_gemm_tn_f32_workspace(int M, int N, int K) {
@@ -1127,7 +1141,9 @@ extern "C" int xps_gemm_tn_f32(const float* A, const xps_rowmap* ra_, const floa
 }
 
 namespace {
-int build_group(const xps_tn_problem* probs, int n, TnGroup& g, size_t& ws_floats, int big_choice = -1) {
+// The whole plan of a grouped launch: the per-problem split / tile class in `g` (the kernels' argument), and in `route` what the
+// entry point launches besides (XPS_GEMM_ROUTE_TN_*: the 128-tile instantiation, 32-deep 256-tile stages, block order, reduce).
+int build_group(const xps_tn_problem* probs, int n, TnGroup& g, size_t& ws_floats, int& route, int big_choice = -1) {
     if (n < 1 || n > TN_MAXP) return -1;
     // (default 512; 768 until the flat reduce existed: 512 + flat is -5 % on the cfg-2 step, -1.7 % on configs[3])
     const int target_blocks = (int)xps_sw::get(xps_sw::TN_BLOCKS);
@@ -1235,6 +1251,22 @@ int build_group(const xps_tn_problem* probs, int n, TnGroup& g, size_t& ws_float
         ws_floats = (size_t)off;
         g.uniform = 1;
     }
+    // a 128-tile problem with an edge / with an XPS_FMT_SPLIT4 operand: the kernel instantiation that masks / that reads the flags.
+    // 32-deep stages of the 256-tile kernel: measured, the [k][x] x [k][x] form gains nothing from them (its fetches are full lines
+    // already) and loses 1-5 % to the larger LDS block: 16-deep unless XPS_GEMM_BIG_DEEP_TN=1 (and every k range allows it)
+    bool edge = false, anypre = false, deep = blocks_big > 0 && big_deep_allowed() && xps_sw::on(xps_sw::GEMM_BIG_DEEP_TN);
+    int max_splits = 1;
+    for (int i = 0; i < n; ++i) {
+        const TnProb& P = g.p[i];
+        const bool pre = (P.vecA | P.vecB) & 2;
+        if (P.big) deep = deep && P.kchunk % 32 == 0 && P.K % 32 == 0 && !pre;
+        else { edge = edge || (P.M % BM) || (P.N % BN); anypre = anypre || pre; }
+        max_splits = P.splits > max_splits ? P.splits : max_splits;
+    }
+    const long long red_mode = xps_sw::get(xps_sw::TN_REDUCE);
+    route = (edge ? XPS_GEMM_ROUTE_TN_EDGE : 0) | (bf_mode() ? XPS_GEMM_ROUTE_TN_BF : 0) | (bf_mode() && anypre ? XPS_GEMM_ROUTE_TN_PRE : 0) |
+            (deep ? XPS_GEMM_ROUTE_TN_DEEP : 0) | (g.uniform ? XPS_GEMM_ROUTE_TN_UNIFORM : 0) |
+            ((red_mode == 1 || (red_mode == 0 && max_splits <= 32)) ? XPS_GEMM_ROUTE_TN_FLAT : 0);
     return 0;
 }
 }  // namespace
@@ -1243,7 +1275,8 @@ extern "C" size_t xps_gemm_tn_grouped_f32_workspace(const xps_tn_problem* probs,
     // the larger of both tilings: the size must not depend on the precision mode / tile switch at launch time
     TnGroup g;
     size_t fl0 = 0, fl1 = 0;
-    if (!probs || build_group(probs, n, g, fl0, 0) || build_group(probs, n, g, fl1, 1)) return 0;
+    int route = 0;
+    if (!probs || build_group(probs, n, g, fl0, route, 0) || build_group(probs, n, g, fl1, route, 1)) return 0;
     return (fl0 > fl1 ? fl0 : fl1) * sizeof(float) + 16;
 }
 
@@ -1252,7 +1285,8 @@ extern "C" int xps_gemm_tn_grouped_f32(const xps_tn_problem* probs, int n, void*
     XPS_CHECK_ARG(probs, "null argument");
     TnGroup g;
     size_t fl = 0;
-    if (build_group(probs, n, g, fl)) {
+    int route = 0;
+    if (build_group(probs, n, g, fl, route)) {
         xps_set_error("xps_gemm_tn_grouped_f32: invalid problem list (1..%d problems, non-null pointers, M,N >= 1; XPS_FMT_SPLIT4 "
                       "operands: bf16x3 mode, 16-byte aligned rows, M / N multiples of 4)", TN_MAXP);
         return XPS_E_INVALID;
@@ -1261,54 +1295,52 @@ extern "C" int xps_gemm_tn_grouped_f32(const xps_tn_problem* probs, int n, void*
         xps_set_error("xps_gemm_tn_grouped_f32: workspace too small or misaligned");
         return XPS_E_WORKSPACE;
     }
-    bool edge = false;
-    for (int i = 0; i < n; ++i) edge = edge || (!g.p[i].big && ((probs[i].M % BM) || (probs[i].N % BN)));
-    const bool bf = bf_mode();
-    bool anypre = false;                   // a 128-tile problem with an XPS_FMT_SPLIT4 operand: the kernel instantiation that reads the flags
-    for (int i = 0; i < n; ++i) anypre = anypre || (!g.p[i].big && ((g.p[i].vecA | g.p[i].vecB) & 2));
+    const hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
     if (g.total_blocks_big > 0) {
         static const bool ready = big_prepare(gemm_big_tn_kernel<false>, BIG_TN_LDS) && big_prepare(gemm_big_tn_kernel<true>, BIG_LDS32);
         if (!ready) {
             xps_set_error("xps_gemm_tn_grouped_f32: cannot reserve %d bytes of LDS", BIG_LDS32 > BIG_TN_LDS ? BIG_LDS32 : BIG_TN_LDS);
             return XPS_E_HIP;
         }
-        // measured: the [k][x] x [k][x] form gains nothing from 32-deep stages (its fetches are full lines already) and loses
-        // 1-5 % to the larger LDS block: 16-deep unless XPS_GEMM_BIG_DEEP_TN=1
-        bool deep = big_deep_allowed() && xps_sw::on(xps_sw::GEMM_BIG_DEEP_TN);
-        for (int i = 0; i < n; ++i) deep = deep && (!g.p[i].big || (g.p[i].kchunk % 32 == 0 && g.p[i].K % 32 == 0 && !((g.p[i].vecA | g.p[i].vecB) & 2)));
-        if (deep)
-            hipLaunchKernelGGL(gemm_big_tn_kernel<true>, dim3(g.total_blocks_big), dim3(xps_big::NTHR), BIG_LDS32, (hipStream_t)stream, g,
-                               (float*)workspace);
+        if (route & XPS_GEMM_ROUTE_TN_DEEP)
+            hipLaunchKernelGGL(gemm_big_tn_kernel<true>, dim3(g.total_blocks_big), dim3(xps_big::NTHR), BIG_LDS32, st, g, ws);
         else
-            hipLaunchKernelGGL(gemm_big_tn_kernel<false>, dim3(g.total_blocks_big), dim3(xps_big::NTHR), BIG_TN_LDS, (hipStream_t)stream, g,
-                           (float*)workspace);
+            hipLaunchKernelGGL(gemm_big_tn_kernel<false>, dim3(g.total_blocks_big), dim3(xps_big::NTHR), BIG_TN_LDS, st, g, ws);
         XPS_CHECK_LAUNCH();
     }
-    if (g.total_blocks == 0) {
-    } else if (bf && edge && anypre)
-        hipLaunchKernelGGL((gemm_tn_grouped_kernel<true, true, true>), dim3(g.total_blocks), dim3(256), 0, (hipStream_t)stream, g, (float*)workspace);
-    else if (bf && anypre)
-        hipLaunchKernelGGL((gemm_tn_grouped_kernel<false, true, true>), dim3(g.total_blocks), dim3(256), 0, (hipStream_t)stream, g, (float*)workspace);
-    else if (bf && edge)
-        hipLaunchKernelGGL((gemm_tn_grouped_kernel<true, true>), dim3(g.total_blocks), dim3(256), 0, (hipStream_t)stream, g, (float*)workspace);
-    else if (bf)
-        hipLaunchKernelGGL((gemm_tn_grouped_kernel<false, true>), dim3(g.total_blocks), dim3(256), 0, (hipStream_t)stream, g, (float*)workspace);
-    else if (edge)
-        hipLaunchKernelGGL((gemm_tn_grouped_kernel<true, false>), dim3(g.total_blocks), dim3(256), 0, (hipStream_t)stream, g, (float*)workspace);
-    else
-        hipLaunchKernelGGL((gemm_tn_grouped_kernel<false, false>), dim3(g.total_blocks), dim3(256), 0, (hipStream_t)stream, g, (float*)workspace);
+#define XPS_TN_CASE(EDGE_, BF_, PRE_)                                                                                        \
+    case (EDGE_ ? XPS_GEMM_ROUTE_TN_EDGE : 0) | (BF_ ? XPS_GEMM_ROUTE_TN_BF : 0) | (PRE_ ? XPS_GEMM_ROUTE_TN_PRE : 0):             \
+        hipLaunchKernelGGL((gemm_tn_grouped_kernel<EDGE_, BF_, PRE_>), dim3(g.total_blocks), dim3(256), 0, st, g, ws);             \
+        break
+    if (g.total_blocks > 0)
+        switch (route & (XPS_GEMM_ROUTE_TN_EDGE | XPS_GEMM_ROUTE_TN_BF | XPS_GEMM_ROUTE_TN_PRE)) {
+            XPS_TN_CASE(false, false, false); XPS_TN_CASE(true, false, false);
+            XPS_TN_CASE(false, true, false); XPS_TN_CASE(true, true, false);
+            XPS_TN_CASE(false, true, true); XPS_TN_CASE(true, true, true);
+        }
+#undef XPS_TN_CASE
     XPS_CHECK_LAUNCH();
-    int max_splits = 1;
-    for (int i = 0; i < n; ++i) max_splits = g.p[i].splits > max_splits ? g.p[i].splits : max_splits;
-    const long long red_mode = xps_sw::get(xps_sw::TN_REDUCE);
-    if (red_mode == 1 || (red_mode == 0 && max_splits <= 32))
-        hipLaunchKernelGGL(gemm_tn_grouped_reduce_flat, dim3(cdiv(g.total_out, 256 * 4)), dim3(256), 0, (hipStream_t)stream, g,
-                           (const float*)workspace);
+    if (route & XPS_GEMM_ROUTE_TN_FLAT)
+        hipLaunchKernelGGL(gemm_tn_grouped_reduce_flat, dim3(cdiv(g.total_out, 256 * 4)), dim3(256), 0, st, g, (const float*)ws);
     else
-        hipLaunchKernelGGL(gemm_tn_grouped_reduce, dim3(cdiv(g.total_out, RED_OUT * 4)), dim3(256), 0, (hipStream_t)stream, g,
-                       (const float*)workspace);
+        hipLaunchKernelGGL(gemm_tn_grouped_reduce, dim3(cdiv(g.total_out, RED_OUT * 4)), dim3(256), 0, st, g, (const float*)ws);
     XPS_CHECK_LAUNCH();
     return XPS_OK;
+}
+
+// the plan xps_gemm_tn_grouped_f32 launches (xps.h)
+extern "C" int xps_gemm_tn_grouped_route(const xps_tn_problem* probs, int n, int* cls, int* splits, int* kchunk) {
+    TnGroup g;
+    size_t fl = 0;
+    int route = 0;
+    if (!probs || build_group(probs, n, g, fl, route)) return XPS_E_INVALID;
+    for (int i = 0; i < n; ++i) {
+        if (cls) cls[i] = g.p[i].big;
+        if (splits) splits[i] = g.p[i].splits;
+        if (kchunk) kchunk[i] = g.p[i].kchunk;
+    }
+    return route;
 }
 
 int xps_internal_gemm_mode() { return (int)xps_sw::get(xps_sw::GEMM_PRECISION); }

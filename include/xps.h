@@ -133,6 +133,63 @@ size_t xps_gemm_tn_grouped_f32_workspace(const xps_tn_problem* probs, int n);
 int xps_gemm_tn_grouped_f32(const xps_tn_problem* probs, int n, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* Which kernel a product runs: the one dispatch decision of nt / nn / nn2 / nt_multi as a query (host logic only: it follows
+ * the switches and the device's CU count like the launches do, and calls the function the launches call).  `form` names the
+ * entry point; the other arguments are the entry point's own.  Pointers are looked at for their alignment, never through --
+ * except B of XPS_GEMM_FORM_NT_MULTI, the HOST array of nprob device pointers.  A2 / B2 / K2: nn2's second pair (its K1 is K),
+ * ignored by the other forms; nprob: nt_multi only.
+ * Returns the XPS_GEMM_ROUTE_* code of the leading launch.  *lead_rows: the rows it covers; where that is less than M (a
+ * 256-tile launch keeps the whole rounds of tiles) *tail_route is the code of the launch that takes the rows behind them,
+ * else XPS_GEMM_ROUTE_NONE.  Both out-parameters may be NULL.  REFUSED: the entry point returns XPS_E_INVALID (also returned
+ * for arguments the entry point rejects); NONE: M or N is 0, nothing is launched.
+ *   SMALL_M         gemm_small_kernel (M <= 16)
+ *   SKINNY          nn / nn2: one 256-wide LDS-DMA tile per 256 rows, N < 256 (gemm_big_kernel<.., 5>)
+ *   BIG + f         256 x 256 tiles, 16-deep register-staged loop; nt / nn / nn2: f = 0..3 (bit 0: A is XPS_FMT_SPLIT4, bit 1: B
+ *                   is), one instantiation each; nt_multi: f = 0, one instantiation for all formats
+ *   BIG_DEEP        256 x 256 tiles, 32-deep stages (XPS_GEMM_BIG_DEEP=1)
+ *   BIG_DMA         256 x 256 tiles, LDS-DMA loop (both operands XPS_FMT_SPLIT4)
+ *   TILE | flags    gemm_f32_kernel / gemm_nt_multi_kernel: _128 = 128-row tiles (else 64), _EDGE = masked edges, _BF = bf16x3
+ *                   products (else fp32 MFMA), _PRE = an XPS_FMT_SPLIT4 operand (implies _BF)
+ *   PROJ_WS + KT    nt_multi: weight-stationary projection kernel, KT = 2 ceil(K / 32) = 2, 4 .. 16 */
+#define XPS_GEMM_FORM_NT 0
+#define XPS_GEMM_FORM_NN 1
+#define XPS_GEMM_FORM_NN2 2
+#define XPS_GEMM_FORM_NT_MULTI 3
+#define XPS_GEMM_ROUTE_REFUSED 0
+#define XPS_GEMM_ROUTE_NONE 1
+#define XPS_GEMM_ROUTE_SMALL_M 2
+#define XPS_GEMM_ROUTE_SKINNY 3
+#define XPS_GEMM_ROUTE_BIG 8
+#define XPS_GEMM_ROUTE_BIG_DEEP 12
+#define XPS_GEMM_ROUTE_BIG_DMA 13
+#define XPS_GEMM_ROUTE_TILE 16
+#define XPS_GEMM_ROUTE_TILE_128 1
+#define XPS_GEMM_ROUTE_TILE_EDGE 2
+#define XPS_GEMM_ROUTE_TILE_BF 4
+#define XPS_GEMM_ROUTE_TILE_PRE 8
+#define XPS_GEMM_ROUTE_PROJ_WS 32
+int xps_gemm_route(int form, const float* A, const xps_rowmap* ra, const void* B, const xps_rowmap* rb, const float* A2,
+                   const float* B2, const xps_rowmap* rc, int M, int N, int K, int K2, int nprob, int* lead_rows,
+                   int* tail_route);
+/* The plan xps_gemm_tn_grouped_f32 launches for a problem list (the function it calls; host logic only).  Per problem, into
+ * arrays of n ints (each may be NULL): cls = XPS_GEMM_TN_CLASS_*, splits = its k-split count, kchunk = the k rows of a split.
+ * Returns the group's XPS_GEMM_ROUTE_TN_* flags or-ed together, or XPS_E_INVALID where the launch refuses the list.
+ *   _EDGE, _BF, _PRE  the gemm_tn_grouped_kernel<EDGE, BF, PRE> instantiation that serves the 128-tile problems (launched when
+ *                     there is one): an edge tile / bf16x3 products / an XPS_FMT_SPLIT4 operand among them
+ *   _DEEP             the 256-tile problems run gemm_big_tn_kernel<true> (32-deep stages), else <false> (launched when there is one)
+ *   _UNIFORM          one common split count, blocks ordered by k-chunk first (XPS_TN_UNIFORM=1)
+ *   _FLAT             gemm_tn_grouped_reduce_flat, else gemm_tn_grouped_reduce (XPS_TN_REDUCE) */
+#define XPS_GEMM_TN_CLASS_128 0       /* 128 x 128 tiles */
+#define XPS_GEMM_TN_CLASS_BIG 1       /* 256 x 256 tiles, register-staged loop */
+#define XPS_GEMM_TN_CLASS_BIG_DMA 2   /* 256 x 256 tiles, LDS-DMA loop */
+#define XPS_GEMM_ROUTE_TN_EDGE 1
+#define XPS_GEMM_ROUTE_TN_BF 2
+#define XPS_GEMM_ROUTE_TN_PRE 4
+#define XPS_GEMM_ROUTE_TN_DEEP 8
+#define XPS_GEMM_ROUTE_TN_UNIFORM 16
+#define XPS_GEMM_ROUTE_TN_FLAT 32
+int xps_gemm_tn_grouped_route(const xps_tn_problem* probs, int n, int* cls, int* splits, int* kchunk);
+
 /* out[c] (+)= sum_r X[r][c] (and optionally sum_r X[r][c]^2 into out_sq), two-stage,
  * deterministic.  Bias gradients and BatchNorm batch statistics.               */
 size_t xps_colsum_f32_workspace(int rows, int cols);

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_route_ref as R
+
 pytestmark = pytest.mark.gpu
 
 from cross_patient_speech_decoding_amd import _build, _switches  # noqa: E402
@@ -44,6 +46,11 @@ def tiles():
     l.xps_set_gemm_precision(old_p)
 
 
+def _is_big(code, fmt=0):
+    """code is the 256-tile register-staged launch for operand formats fmt (bit 0: A split4, bit 1: B split4)"""
+    return code == R.BIG + fmt
+
+
 def _bound(a64, b64_t):
     """1.6e-5 * sum_k |a||b| for a (M, K) @ b_t (K, N)"""
     return 1.6e-5 * (a64.abs() @ b64_t.abs())
@@ -63,6 +70,8 @@ def test_nt_equals_small_tiles_bitwise_and_fp64(K, bias, acc, tiles):
     for t in (0, 1):
         tiles(t)
         Cc = C0.clone()
+        code = R.ask(R.FORM_NT, A, rowmap(K), B, rowmap(K), rowmap(N0), M0, N0, K)[0]
+        assert _is_big(code) if t else R.is_tile(code, pre=False), (t, code)
         xf.gemm_nt(A, B, Cc, M0, N0, K, bias=bv, accumulate=acc)
         outs.append(Cc)
     assert torch.equal(outs[0], outs[1])
@@ -103,8 +112,10 @@ def test_nn_and_nn2_equal_small_tiles_bitwise(tiles):
     for t in (0, 1):
         tiles(t)
         c1 = torch.empty(M0, N0, device='cuda'); c2 = torch.empty(M0, N0, device='cuda')
-        xf.gemm_nn(A1, B1, c1, M0, N0, K1)
         ra, rb, rc = rowmap(K1), rowmap(N0), rowmap(N0)
+        for code in (R.ask(R.FORM_NN, A1, ra, B1, rb, rc, M0, N0, K1)[0], R.ask(R.FORM_NN2, A1, ra, B1, rb, rc, M0, N0, K1, A2=A2, B2=B2, K2=K1)[0]):
+            assert _is_big(code) if t else R.is_tile(code, pre=False), (t, code)
+        xf.gemm_nn(A1, B1, c1, M0, N0, K1)
         call('xps_gemm_nn2_f32', xf._ptr(A1), xf._ptr(B1), K1, xf._ptr(A2), xf._ptr(B2), K1, C.byref(ra), C.byref(rb), xf._ptr(c2),
              C.byref(rc), M0, N0, 0, xf._stream())
         outs.append((c1, c2))
@@ -115,9 +126,11 @@ def test_nn_and_nn2_equal_small_tiles_bitwise(tiles):
     del K2
 
 
-def test_nt_multi_equals_small_tiles_bitwise(tiles):
-    """the input projections of both directions in one launch (GRULayerFn.forward)"""
+def test_nt_multi_equals_small_tiles_bitwise(tiles, switch):
+    """the input projections of both directions in one launch (GRULayerFn.forward); XPS_PROJ_WS=0: with K = 112 the projection
+    kernel would take both legs (the route query showed it), and the 256-tile kernel this test is about would not run"""
     xf = XF()
+    switch(XPS_PROJ_WS=0)
     g = torch.Generator().manual_seed(11)
     M, N, K = 4096, 1536, 112
     A = torch.randn(M, K, generator=g).cuda()
@@ -128,6 +141,8 @@ def test_nt_multi_equals_small_tiles_bitwise(tiles):
         tiles(t)
         Cs = [torch.empty(M, N, device='cuda') for _ in range(2)]
         ra, rb, rc = rowmap(K), rowmap(K), rowmap(N)
+        code = R.ask(R.FORM_NT_MULTI, A, ra, Bs, rb, rc, M, N, K, nprob=2)[0]
+        assert code == R.BIG if t else R.is_tile(code, pre=False), (t, code)
         call('xps_gemm_nt_multi_f32', xf._ptr(A), C.byref(ra), xf._ptr_array(Bs), C.byref(rb), xf._ptr_array(Cs), C.byref(rc),
              xf._ptr_array(bs), 2, M, N, K, xf._stream())
         outs.append(Cs)
@@ -155,12 +170,15 @@ def test_weight_gradient_group_mixes_both_tile_shapes(tiles):
         probs = [xf.tn_problem(dgi, x[:, 512:], dw_a, 1024, 512, K, ra=rowmap(1536), rb=rowmap(ld), rc=rowmap(512), colsum_out=db_a),
                  xf.tn_problem(dgi, x, dw_b, 1536, 1024, K, colsum_out=db_b, accumulate=True),
                  xf.tn_problem(dgi, xs, dw_c, 1536, 100, K)]
+        assert R.ask_tn(probs)[1] == classes
         keep = xf.gemm_tn_grouped(probs, dgi.device)
         torch.cuda.synchronize()
         del keep
         return dw_a, db_a, dw_b, db_b, dw_c
 
+    classes = [R.TN_CLASS_128] * 3
     tiles(0); small = run()
+    classes = [R.TN_CLASS_BIG, R.TN_CLASS_BIG, R.TN_CLASS_128]
     tiles(1); big = run()
     d64, x64 = dgi.double(), x.double()
     refs = [d64[:, :1024].T @ x64[:, 512:], d64.sum(0)[:1024], 1 + d64.T @ x64, 1 + d64.sum(0), d64.T @ xs.double()]
@@ -198,16 +216,20 @@ def test_weight_gradient_lds_dma_loop_equals_register_staged_loop_bitwise(K, M, 
     def run():
         out = C0.clone() if acc else torch.empty(M, N, device='cuda')
         db = torch.zeros(M, device='cuda') if cs else None
-        keep = xf.gemm_tn_grouped([xf.tn_problem(A4, Bv, out, M, N, K, ra=rowmap(M, fmt=1), rb=rowmap(ldb, fmt=1), rc=rowmap(N),
-                                                 colsum_out=db, accumulate=acc)], 'cuda')
+        probs = [xf.tn_problem(A4, Bv, out, M, N, K, ra=rowmap(M, fmt=1), rb=rowmap(ldb, fmt=1), rc=rowmap(N), colsum_out=db, accumulate=acc)]
+        assert R.ask_tn(probs)[1] == [cls]
+        keep = xf.gemm_tn_grouped(probs, 'cuda')
         torch.cuda.synchronize()
         del keep
         return out, db
 
     tiles(1)
+    cls = R.TN_CLASS_BIG_DMA
     switch(XPS_GEMM_DMA=1); dma, dma_cs = run()
     again, again_cs = run()
+    cls = R.TN_CLASS_BIG
     switch(XPS_GEMM_DMA=0); reg, reg_cs = run()
+    cls = R.TN_CLASS_128
     tiles(0); small, small_cs = run()
     assert torch.equal(dma, reg) and torch.equal(dma, again)
     a64, b64 = A.double(), Bfull.double()[:, boff:boff + N]
@@ -241,7 +263,15 @@ def test_direct_forms_lds_dma_loop_equals_register_staged_loop_bitwise(K, tiles,
     A4, A24, B4, Bt4, Bt24 = (xf.split4(t) for t in (A, A2, B, Bt, Bt2))
     ra, rbk, rbn, rc = rowmap(K, fmt=1), rowmap(K, fmt=1), rowmap(N0, fmt=1), rowmap(N0)
 
-    def run():
+    def run(leg):
+        # K = 32 is below the 256-tile kernels' 64: there all three legs are tile launches, and the projections run proj_ws_kernel
+        want = {'dma': R.BIG_DMA, 'reg': R.BIG + 3}.get(leg) if K >= 64 else None
+        codes = [R.ask(R.FORM_NT, A4, ra, B4, rbk, rc, M0, N0, K)[0], R.ask(R.FORM_NN, A4, ra, Bt4, rbn, rc, M0, N0, K)[0],
+                 R.ask(R.FORM_NN2, A4, ra, Bt4, rbn, rc, M0, N0, K, A2=A24, B2=Bt24, K2=K)[0]]
+        assert all(c == want if want else R.is_tile(c, pre=True) for c in codes), (leg, codes)
+        code = R.ask(R.FORM_NT_MULTI, A4, ra, [B4, B4], rbk, rc, M0, N0, K, nprob=2)[0]
+        want = R.PROJ_WS + 2 * ((K + 31) // 32) if K <= 256 else {'dma': R.BIG_DMA, 'reg': R.BIG}.get(leg)      # (K <= 256: on every leg)
+        assert code == want if want else R.is_tile(code, pre=True), (leg, code)
         c_nt = C0.clone()
         xf.gemm_nt(A4, B4, c_nt, M0, N0, K, bias=bias, accumulate=True, ra=ra, rb=rbk)
         c_nn = torch.empty(M0, N0, device='cuda')
@@ -256,9 +286,9 @@ def test_direct_forms_lds_dma_loop_equals_register_staged_loop_bitwise(K, tiles,
         return c_nt, c_nn, c_nn2, cs[0], cs[1]
 
     tiles(1)
-    switch(XPS_GEMM_DMA=1); dma = run()
-    switch(XPS_GEMM_DMA=0); reg = run()
-    tiles(0); small = run()
+    switch(XPS_GEMM_DMA=1); dma = run('dma')
+    switch(XPS_GEMM_DMA=0); reg = run('reg')
+    tiles(0); small = run('small')
     for a, b, c in zip(dma, reg, small):
         assert torch.equal(a, b) and torch.equal(a, c)
     a64 = A.double()
@@ -284,7 +314,9 @@ def test_skinny_input_gradient_on_the_lds_dma_loop_equals_edge_tiles_bitwise(N, 
     A14, A24 = xf.split4(A1), xf.split4(A2)
     ra, rc = rowmap(K, fmt=1), rowmap(N)
 
-    def nn2(b1, b2, rb):
+    def nn2(b1, b2, rb, route):
+        code = R.ask(R.FORM_NN2, A14, ra, b1, rb, rc, M, N, K, A2=A24, B2=b2, K2=K)[0]
+        assert code == route, (code, route)
         out = torch.full((M, N), 7.0, device='cuda')
         call('xps_gemm_nn2_f32', xf._ptr(A14), xf._ptr(b1), K, xf._ptr(A24), xf._ptr(b2), K, C.byref(ra), C.byref(rb), xf._ptr(out),
              C.byref(rc), M, N, 0, xf._stream())
@@ -295,9 +327,10 @@ def test_skinny_input_gradient_on_the_lds_dma_loop_equals_edge_tiles_bitwise(N, 
     switch(XPS_GEMM_DMA=1)
     P1, P2 = xf.split4_pad(W1, 256), xf.split4_pad(W2, 256)
     assert P1.shape == (K, 256) and float(P1[:, N:].abs().max()) == 0.0
-    dma = nn2(P1, P2, rowmap(256, fmt=1))
-    edge = nn2(xf.split4(W1), xf.split4(W2), rowmap(N, fmt=1))
-    plain = nn2(W1, W2, rowmap(N))
+    edge_tiles = R.TILE | R.TILE_EDGE | R.TILE_BF                        # 64-row tiles
+    dma = nn2(P1, P2, rowmap(256, fmt=1), R.SKINNY)
+    edge = nn2(xf.split4(W1), xf.split4(W2), rowmap(N, fmt=1), edge_tiles | R.TILE_PRE)
+    plain = nn2(W1, W2, rowmap(N), edge_tiles | R.TILE_PRE)
     assert torch.equal(dma, edge) and torch.equal(dma, plain)
     ref = A1.double() @ W1.double() + A2.double() @ W2.double()
     assert bool(((dma.double() - ref).abs() <= _bound(A1.double(), W1.double()) + _bound(A2.double(), W2.double()) + 1e-5).all())
@@ -312,7 +345,9 @@ def test_opt_in_32_deep_stages_same_bits():
     import subprocess
     import sys
     code = (
-        "import torch, ctypes as C\n"
+        "import sys, torch, ctypes as C\n"
+        "sys.path.insert(0, 'tests')\n"
+        "import gemm_route_ref as R\n"
         "from cross_patient_speech_decoding_amd._lib import lib, call, rowmap\n"
         "from cross_patient_speech_decoding_amd.nn_models import functional as xf\n"
         "l = lib(); l.xps_set_gemm_precision(1)\n"
@@ -323,6 +358,8 @@ def test_opt_in_32_deep_stages_same_bits():
         "for t in (0, 1):\n"
         "    l.xps_set_gemm_big_tiles(t)\n"
         "    c1 = torch.empty(M, N, device='cuda'); c2 = torch.empty(M, N, device='cuda')\n"
+        "    codes = [R.ask(R.FORM_NT, A, rowmap(K), B, rowmap(K), rowmap(N), M, N, K)[0], R.ask(R.FORM_NN, A, rowmap(K), Bt, rowmap(N), rowmap(N), M, N, K)[0]]\n"
+        "    assert all(c == R.BIG_DEEP if t else R.is_tile(c, pre=False) for c in codes), (t, codes)\n"
         "    xf.gemm_nt(A, B, c1, M, N, K); xf.gemm_nn(A, Bt, c2, M, N, K)\n"
         "    outs.append((c1, c2))\n"
         "assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])\n"

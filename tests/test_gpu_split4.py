@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_route_ref as R
+
 pytestmark = pytest.mark.gpu
 
 from cross_patient_speech_decoding_amd import _build, _switches  # noqa: E402
@@ -84,6 +86,15 @@ def test_split4_kernel_matches_the_host_restatement_and_dropout_values():
     assert (dropped == 0).float().mean().item() > 0.2
 
 
+def assert_route(code, big, fa, fb, K, multi=False):
+    """the leg's launch: 256 x 256 tiles (the LDS-DMA loop where both operands are split4 and K % 32 == 0) or a 64- / 128-row tile
+    kernel, which reads the split4 flags exactly when an operand has them"""
+    if big:
+        assert code == (R.BIG_DMA if fa and fb and K % 32 == 0 else R.BIG if multi else R.BIG + fa + 2 * fb), (code, fa, fb)
+    else:
+        assert R.is_tile(code, pre=bool(fa or fb)), (code, fa, fb)
+
+
 # (M, N, K): edge tiles, 64-row tiles, 128-row tiles, and shapes the 256 x 256 kernels take (>= 192 big tiles for nt / nn)
 SHAPES = [(37, 72, 100), (300, 384, 256), (4096, 100, 128), (4096, 768, 256), (8192, 1536, 512)]
 
@@ -94,13 +105,18 @@ def test_nt_nn_products_from_split4_operands_are_bit_identical(M, N, K):
     A, Bt, Bn = rnd(M, K, seed=M), rnd(N, K, seed=N + 1), rnd(K, N, seed=K + 2)
     bias = rnd(N, seed=5)
     A4, Bt4, Bn4 = split4(A), split4(Bt), split4(Bn)
+    big = (M, N, K) == SHAPES[-1]
+    assert_route(R.ask(R.FORM_NT, A, rowmap(K), Bt, rowmap(K), rowmap(N), M, N, K)[0], big, 0, 0, K)
     ref = F.gemm_nt(A, Bt, torch.empty(M, N, device='cuda'), M, N, K, bias=bias)
     for fa, fb in [(1, 0), (0, 1), (1, 1)]:
+        assert_route(R.ask(R.FORM_NT, A4 if fa else A, rowmap(K, fmt=fa), Bt4 if fb else Bt, rowmap(K, fmt=fb), rowmap(N), M, N, K)[0], big, fa, fb, K)
         out = F.gemm_nt(A4 if fa else A, Bt4 if fb else Bt, torch.empty(M, N, device='cuda'), M, N, K, bias=bias,
                         ra=rowmap(K, fmt=fa), rb=rowmap(K, fmt=fb))
         assert torch.equal(out, ref), (fa, fb)
+    assert_route(R.ask(R.FORM_NN, A, rowmap(K), Bn, rowmap(N), rowmap(N), M, N, K)[0], big, 0, 0, K)
     ref = F.gemm_nn(A, Bn, torch.empty(M, N, device='cuda'), M, N, K)
     for fa, fb in [(1, 0), (0, 1), (1, 1)]:
+        assert_route(R.ask(R.FORM_NN, A4 if fa else A, rowmap(K, fmt=fa), Bn4 if fb else Bn, rowmap(N, fmt=fb), rowmap(N), M, N, K)[0], big, fa, fb, K)
         out = F.gemm_nn(A4 if fa else A, Bn4 if fb else Bn, torch.empty(M, N, device='cuda'), M, N, K,
                         ra=rowmap(K, fmt=fa), rb=rowmap(N, fmt=fb))
         assert torch.equal(out, ref), (fa, fb)
@@ -115,6 +131,7 @@ def test_nn2_and_nt_multi_from_split4_operands_are_bit_identical(M, N, K):
     def nn2(a1, a2, b1, b2, fa, fb):
         out = torch.empty(M, N, device='cuda')
         ra, rb, rc = rowmap(K, fmt=fa), rowmap(N, fmt=fb), rowmap(N)
+        assert_route(R.ask(R.FORM_NN2, a1, ra, b1, rb, rc, M, N, K, A2=a2, B2=b2, K2=K)[0], M == 40960, fa, fb, K)
         call('xps_gemm_nn2_f32', a1.data_ptr(), b1.data_ptr(), K, a2.data_ptr(), b2.data_ptr(), K, C.byref(ra), C.byref(rb),
              out.data_ptr(), C.byref(rc), M, N, 0, F._stream())
         return out
@@ -130,6 +147,7 @@ def test_nn2_and_nt_multi_from_split4_operands_are_bit_identical(M, N, K):
     def ntm(a, w, fa, fb):
         outs = [torch.empty(M, N, device='cuda') for _ in range(2)]
         ra, rb, rc = rowmap(K, fmt=fa), rowmap(K, fmt=fb), rowmap(N)
+        assert_route(R.ask(R.FORM_NT_MULTI, a, ra, w, rb, rc, M, N, K, nprob=2)[0], M == 40960, fa, fb, K, multi=True)
         call('xps_gemm_nt_multi_f32', a.data_ptr(), C.byref(ra), F._ptr_array(w), C.byref(rb), F._ptr_array(outs), C.byref(rc),
              F._ptr_array(bs), 2, M, N, K, F._stream())
         return outs
@@ -148,7 +166,10 @@ def test_grouped_weight_gradients_from_split4_operands(Kr, M, N):
 
     def run(a, b, fa, fb):
         out, cs = torch.empty(M, N, device='cuda'), torch.empty(M, device='cuda')
-        F.gemm_tn_grouped([F.tn_problem(a, b, out, M, N, Kr, ra=rowmap(M, fmt=fa), rb=rowmap(N, fmt=fb), colsum_out=cs)], 'cuda')
+        probs = [F.tn_problem(a, b, out, M, N, Kr, ra=rowmap(M, fmt=fa), rb=rowmap(N, fmt=fb), colsum_out=cs)]
+        big = M % 256 == 0 and N % 256 == 0
+        assert R.ask_tn(probs)[1] == [(R.TN_CLASS_BIG_DMA if fa and fb else R.TN_CLASS_BIG) if big else R.TN_CLASS_128]
+        F.gemm_tn_grouped(probs, 'cuda')
         torch.cuda.synchronize()
         return out, cs
 
@@ -329,13 +350,17 @@ def test_weight_stationary_projection_equals_the_tile_kernels_bitwise(M, N, K, n
     def run(a, w, fa, fb):
         outs = [torch.full((M, N), float('nan'), device='cuda') for _ in range(nprob)]
         ra, rb, rc = rowmap(K, fmt=fa), rowmap(K, fmt=fb), rowmap(N)
+        code = R.ask(R.FORM_NT_MULTI, a, ra, w, rb, rc, M, N, K, nprob=nprob)[0]
+        assert code == R.PROJ_WS + 2 * ((K + 31) // 32) if ws else R.is_tile(code, pre=bool(fa or fb)), (ws, code)
         call('xps_gemm_nt_multi_f32', a.data_ptr(), C.byref(ra), F._ptr_array(w), C.byref(rb), F._ptr_array(outs), C.byref(rc),
              F._ptr_array(bs), nprob, M, N, K, F._stream())
         torch.cuda.synchronize()
         return outs
 
+    ws = False
     switch(XPS_PROJ_WS=0)
     ref = run(A, W, 0, 0)
+    ws = True
     switch(XPS_PROJ_WS=1)
     for fa, fb in [(0, 0), (1, 0), (1, 1)]:
         got = run(split4(A) if fa else A, [split4(w) for w in W] if fb else W, fa, fb)
