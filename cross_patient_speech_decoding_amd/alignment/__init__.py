@@ -5,4 +5,4 @@ from .AlignMCCA import AlignMCCA  # noqa: F401
 from .JointPCA import JointPCA  # noqa: F401
 from .alignment_utils import cnd_avg, extract_group_conditions, label2str  # noqa: F401
 from .pca import PCA, GramPCA, PCA_SPECTRUM_LIMIT, fit_many  # noqa: F401
-from .fold_align import FoldAlignment, fit_folds, fold_plan  # noqa: F401
+from .fold_align import FoldAlignment, fit_folds, fit_folds_multi, fold_plan  # noqa: F401

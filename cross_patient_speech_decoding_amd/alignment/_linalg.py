@@ -904,6 +904,65 @@ def gram_grouped(problems):
     return tab, tiles, ws
 
 
+RBF_WORDS, VAR_WORDS = 8, 8                                 # XPS_RBF_GROUPED_WORDS, XPS_VAR_GROUPED_WORDS of include/xps.h
+
+
+def rbf_tiles(rows):
+    """The int32 tile table of a grouped rbf launch (pure numpy): one row {problem, ti, tj} for every 64 x 64 tile of every problem,
+    problems in order, tj fastest.  rows[p]: problem p's row count."""
+    t = [-(-int(n) // 64) for n in rows]
+    return _tile_table([(c, c) for c in t]) if t else np.zeros((0, 3), dtype=np.int32)
+
+
+def rbf_grouped(problems):
+    """problems: list of (G, gamma, K): K[i][j] = exp(-gamma (G[i][i] + G[j][j] - 2 G[i][j])) for every problem in ONE
+    xps_rbf_grouped_from_gram_f64 launch -- xps_rbf_from_gram_f64's bits with the diagonal of G as norms.  G, K (n, n) float64
+    device matrices with contiguous rows (slices of larger tensors are fine); several problems may share a G; no K may overlap a
+    G of the call.  Returns the host tables of the call, which the caller keeps until it has synchronised with the stream."""
+    n = len(problems)
+    if n == 0:
+        return None
+    tab = np.zeros((n, RBF_WORDS), dtype=np.int64)
+    for i, (G, gamma, K) in enumerate(problems):
+        _check_matrix(G, 'rbf_grouped G')
+        _check_matrix(K, 'rbf_grouped K')
+        rows = G.shape[0]
+        gamma = float(gamma)
+        if G.dtype != F64 or K.dtype != F64 or tuple(G.shape) != (rows, rows) or tuple(K.shape) != (rows, rows) or rows >= 2 ** 31 - 64:
+            raise ValueError('rbf_grouped: G and K must be float64 (n, n) matrices of one size')
+        if not (np.isfinite(gamma) and gamma >= 0):
+            raise ValueError(f'rbf_grouped: gamma must be finite and non-negative; got {gamma}')
+        tab[i, :6] = [G.data_ptr(), G.stride(0), rows, np.float64(gamma).view(np.int64), K.data_ptr(), K.stride(0)]
+    tab, tiles = np.ascontiguousarray(tab.reshape(-1)), rbf_tiles(tab[:, 2])
+    nb = int(lib().xps_rbf_grouped_from_gram_f64_workspace(n, len(tiles)))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=device())
+    call('xps_rbf_grouped_from_gram_f64', tab.ctypes.data, n, tiles.ctypes.data, len(tiles), ws.data_ptr(), nb, stream())
+    return tab, tiles, ws
+
+
+def var_grouped(blocks):
+    """blocks: list of (V, first, rows): the population variance (numpy's ``.var()``) of all elements of V[first:first + rows], for
+    every block in ONE xps_var_grouped_f64 launch, float64 in two passes.  V (n, D) float32 / float64 device matrices with contiguous
+    rows.  Returns the float64 device vector of the variances (0 for an empty block) and the host table of the call, which the caller
+    keeps until it has synchronised with the stream (downloading the vector does)."""
+    n = len(blocks)
+    out = torch.empty(n, dtype=F64, device=device())
+    if n == 0:
+        return out, None
+    tab = np.zeros((n, VAR_WORDS), dtype=np.int64)
+    for i, (V, first, rows) in enumerate(blocks):
+        _check_matrix(V, 'var_grouped V')
+        first, rows = int(first), int(rows)
+        if first < 0 or rows < 0 or first + rows > V.shape[0] or V.shape[0] >= 2 ** 31 or V.shape[1] >= 2 ** 31:
+            raise ValueError('var_grouped: the rows first .. first + rows - 1 must lie inside V')
+        tab[i, :6] = [V.data_ptr(), _is32(V), V.stride(0), first, rows, V.shape[1]]
+    tab = np.ascontiguousarray(tab.reshape(-1))
+    nb = int(lib().xps_var_grouped_f64_workspace(n))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=device())
+    call('xps_var_grouped_f64', tab.ctypes.data, n, out.data_ptr(), ws.data_ptr(), nb, stream())
+    return out, (tab, ws)
+
+
 def cnd_avg_folds(segments):
     """segments: list of (src, out, trials): out[:] = mean over t in `trials` (in that order, float64 adds) of src[t].
     src (n, ...) and out (...) contiguous float64 device tensors, trials an integer sequence.  ONE launch."""

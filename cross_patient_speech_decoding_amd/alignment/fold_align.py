@@ -25,6 +25,9 @@ Jacobi launches -- one per distinct matrix size -- and the chunks of ``max_bytes
 With ``append_heldout=True`` every fold's pooled tensor has the fold's held-out trials after the pooled rows; they are more
 entries of launch 5 (the fold's own mean and components), so the list above does not grow.
 The O(d^2) glue (whitening factors, M_a, M_b, the maps) is host numpy, as in ``AlignCCA._cca_device``.
+``fit_folds_multi`` fits a list of ``n_components`` values: launches 1-4 and the pooled patients' eigendecompositions once
+(nothing in them looks at ``n_components``), then launches 5-9 once with the folds of every distinct set of component counts
+side by side -- a (value, fold) pair is just another fold to them.
 
 Only ``AlignCCA``'s defaults (type='class', return_space='b_to_a') are supported.
 """
@@ -34,7 +37,7 @@ import torch
 from . import _linalg as LA
 from .AlignCCA import _cca_device, cca_tail
 from .alignment_utils import _cnd_avg_device, label2str
-from .pca import count_components, fit_many, sign_rule
+from .pca import PCA, count_components, eig_many, sign_rule
 
 SPECTRUM_LIMIT = 1e10          # above it rank_from_gram_eigs and LAPACK's rank rule may disagree: the problem takes _cca_device
 
@@ -205,6 +208,41 @@ def _solve_cca(probs):
             p['map'] = p['M_b'] @ np.linalg.pinv(p['M_a'])
 
 
+class _Shared:
+    """What a fold-batched fit computes before ``n_components`` is looked at (launches 1-4 and the pooled patients' covariances
+    and eigendecompositions): ``fit_folds_multi`` computes it once for all its values."""
+
+
+def _ratio_curve(w):
+    """(clipped spectrum, its explained-variance-ratio curve): alignment.PCA's rule on the covariance side."""
+    w = np.clip(w, 0.0, None)
+    total = w.sum()
+    return w, (w / total if total > 0 else np.zeros_like(w))
+
+
+def resolve_counts(n_components, fold_spectra, fold_rows, n_channels, pool_spectra, pool_shapes):
+    """The component counts one ``n_components`` value resolves to (host only): (the target's count in every fold, the count of
+    every pooled patient), two tuples.  ``fold_spectra[f]`` / ``pool_spectra[p]``: the descending covariance spectra;
+    ``fold_rows[f]``: the rows (trials x time) of fold f's training set; ``pool_shapes[p]``: (rows, channels) of patient p.  Two
+    values with equal tuples give the same fit."""
+    folds = tuple(count_components(n_components, _ratio_curve(w)[1], int(n), n_channels) for w, n in zip(fold_spectra, fold_rows))
+    pools = tuple(count_components(n_components, _ratio_curve(w)[1], int(n), int(d)) for w, (n, d) in zip(pool_spectra, pool_shapes))
+    return folds, pools
+
+
+def distinct_counts(n_components_list, fold_spectra, fold_rows, n_channels, pool_spectra, pool_shapes):
+    """(index, firsts): ``index[i]`` numbers the distinct fit entry i of the list resolves to (``resolve_counts``), in order of first
+    appearance, and ``firsts[j]`` is the position in the list of the first entry of fit j (host only)."""
+    seen, index, firsts = {}, [], []
+    for i, nc in enumerate(n_components_list):
+        key = resolve_counts(nc, fold_spectra, fold_rows, n_channels, pool_spectra, pool_shapes)
+        if key not in seen:
+            seen[key] = len(firsts)
+            firsts.append(i)
+        index.append(seen[key])
+    return index, firsts
+
+
 def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 30, append_heldout=False):
     """Fit the target PCA and the P pairwise CCA alignments of EVERY fold of `splits` at once.
 
@@ -213,6 +251,25 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
     per-fold device arrays (Z_f and the pooled tensor) stay within `max_bytes`.  ``append_heldout``: every fold's pooled tensor is
     allocated with room for the fold's held-out trials after the pooled rows and launch 5 fills them (``pool_with_heldout``);
     ``train_pool`` and everything else are what they are without it.  Returns a ``FoldAlignment``."""
+    return _finish(_prepare(X, y_align, pool_data, splits), [n_components], max_bytes, append_heldout)[0]
+
+
+def fit_folds_multi(X, y_align, pool_data, splits, n_components_list, max_bytes=2 ** 30, append_heldout=False):
+    """``[fit_folds(..., n_components=v) for v in n_components_list]``, value for value and bit for bit, with the work that does
+    not depend on ``n_components`` done once for the list: the group moments, the fold covariances and every eigendecomposition of
+    a covariance (launches 1-4 and the pooled patients' PCAs).  Entries that resolve to the same component counts -- the same
+    target count in every fold and the same count for every pooled patient (``resolve_counts``) -- are ONE ``FoldAlignment``
+    object.  Launches 5-9 run once per chunk of ``max_bytes`` with the folds of all distinct objects side by side (a (value, fold)
+    pair is just another fold to them), and a pooled patient's PCA scores once per distinct component count."""
+    sh = _prepare(X, y_align, pool_data, splits)
+    n_components_list = list(n_components_list)
+    index, firsts = distinct_counts(n_components_list, [w for w, _ in sh.fold_eig], sh.n_f, sh.C, [e[0] for e, _, _, _ in sh.pool_eig],
+                                    [(n, d) for _, _, n, d in sh.pool_eig])
+    fits = _finish(sh, [n_components_list[i] for i in firsts], max_bytes, append_heldout)
+    return [fits[j] for j in index]
+
+
+def _prepare(X, y_align, pool_data, splits):
     Xd = LA.to_device(X)
     if Xd.dim() != 3:
         raise ValueError('fit_folds: X must be (trials, time, channels)')
@@ -221,22 +278,14 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
     plan = fold_plan(_np(y_align), [_np(ya) for _, _, ya in pool_data], splits)
     if plan.n_trials != N:
         raise ValueError('fit_folds: y_align and X differ in their number of trials')
-    F, G, P = plan.n_folds, plan.n_groups, len(pool_data)
+    F, G = plan.n_folds, plan.n_groups
 
-    # pooled patients: PCA and condition means once
-    Zp, Bp, pool_n = [], [], []
+    # pooled patients: covariance and eigendecomposition once
     pool_d = [LA.to_device(x) for x, _, _ in pool_data]
     for xd in pool_d:
         if xd.dim() != 3 or xd.shape[1] != T:
             raise ValueError('fit_folds: every pooled patient must be (trials, T, channels) with the target\'s T')
-    pool_pca = fit_many([xd.reshape(-1, xd.shape[-1]) for xd in pool_d], n_components=n_components)
-    for xd, pca, (_, _, ya), pk in zip(pool_d, pool_pca, pool_data, plan.pool_keys):
-        z = pca.transform_device(xd)
-        uniq, b = _cnd_avg_device(z, label2str(_np(ya)))
-        assert np.array_equal(uniq, pk)
-        Zp.append(z.reshape(-1, z.shape[-1]))
-        Bp.append(b.reshape(-1, b.shape[-1]))
-        pool_n.append(xd.shape[0])
+    pool_eig = eig_many([xd.reshape(-1, xd.shape[-1]) for xd in pool_d])
 
     # 1-3: group moments about the all-trial mean -> fold sums
     c_d = LA.col_mean(X2)
@@ -252,16 +301,40 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
     covs = 0.5 * (covs + covs.transpose(0, 2, 1))
     means = c[None, :] + t_f / n_f[:, None]
 
-    # 4: the k fold PCAs
+    # 4: the k fold eigendecompositions
+    sh = _Shared()
+    sh.Xd, sh.X2, sh.plan, sh.pool_data, sh.pool_d, sh.pool_eig = Xd, X2, plan, pool_data, pool_d, pool_eig
+    sh.N, sh.T, sh.C, sh.n_f, sh.means = N, T, C, n_f, means
+    sh.fold_eig = list(LA.eigh_psd_batched(covs))
+    sh.pool_cache = {}
+    return sh
+
+
+def _cut(sh, n_components):
+    """What one ``n_components`` value cuts from the shared spectra (host rules, one upload): the FoldAlignment with its fold PCAs,
+    and per pooled patient the scores Zp and condition means Bp of its PCA -- computed once per (patient, component count)."""
+    plan, C, n_f, means = sh.plan, sh.C, sh.n_f, sh.means
+    F = plan.n_folds
+    Zp, Bp = [], []
+    for p, ((e, mean, n, d), xd, (_, _, ya), pk) in enumerate(zip(sh.pool_eig, sh.pool_d, sh.pool_data, plan.pool_keys)):
+        k = count_components(n_components, _ratio_curve(e[0])[1], n, d)
+        if (p, k) not in sh.pool_cache:
+            pca = PCA(n_components=n_components)._fit_from_eig(e, mean, n, d)
+            assert pca.n_components_ == k
+            z = pca.transform_device(xd)
+            uniq, b = _cnd_avg_device(z, label2str(_np(ya)))
+            assert np.array_equal(uniq, pk)
+            sh.pool_cache[p, k] = (z.reshape(-1, z.shape[-1]), b.reshape(-1, b.shape[-1]))
+        Zp.append(sh.pool_cache[p, k][0])
+        Bp.append(sh.pool_cache[p, k][1])
+
     fa = FoldAlignment()
-    fa.plan, fa._X = plan, Xd
+    fa.plan, fa._X = plan, sh.Xd
     fa.pca_mean_, fa.pca_components_, fa.n_components_, fa.explained_variance_ = [], [], [], []
     fa.explained_variance_ratio_all_ = []
-    for f, (w, V) in enumerate(LA.eigh_psd_batched(covs)):
+    for f, (w, V) in enumerate(sh.fold_eig):
         # alignment.PCA's rules on the covariance side: ratio curve w / sum(w), its component count, sklearn's sign rule
-        w = np.clip(w, 0.0, None)
-        total = w.sum()
-        ratio = w / total if total > 0 else np.zeros_like(w)
+        w, ratio = _ratio_curve(w)
         k = count_components(n_components, ratio, int(n_f[f]), C)
         comps = V.T[:k].copy()
         fa.pca_mean_.append(means[f].copy())
@@ -277,27 +350,45 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
         fa._mean_d.append(flat[o:o + C])
         fa._W_d.append(flat[o + C:o + C + C * kf[f]].view(C, kf[f]))
         o += C + C * kf[f]
+    return fa, Zp, Bp
 
+
+def _finish(sh, values, max_bytes, append_heldout):
+    """Everything of a fit that depends on ``n_components``, for a list of values at once: the cuts of the spectra (``_cut``) and
+    launches 5-9, to which a (value, fold) pair is just another fold.  Returns one FoldAlignment per value."""
+    Xd, X2, plan, N, T = sh.Xd, sh.X2, sh.plan, sh.N, sh.T
+    F, P = plan.n_folds, len(sh.pool_data)
+    pool_n = [xd.shape[0] for xd in sh.pool_d]
     n_train = [len(tr) for tr, _ in plan.splits]
     pool_rows = [n + sum(pool_n) for n in n_train]
     held_rows = [len(te) if append_heldout else 0 for _, te in plan.splits]
-    fa._pool = [None] * F
-    fa._pool_all = [None] * F if append_heldout else None
-    fa.M_a_ = [[None] * P for _ in range(F)]
-    fa.M_b_ = [[None] * P for _ in range(F)]
-    fa.canon_corrs_ = [[None] * P for _ in range(F)]
-    fa.maps_ = [[None] * P for _ in range(F)]
-    fa.fallbacks_ = []
-    per_fold = [N * T * kf[f] * 8 + (pool_rows[f] + held_rows[f]) * T * kf[f] * 4 for f in range(F)]
-    for chunk in _fold_chunks(per_fold, max_bytes):
+    fas, Zps, Bps = [], [], []
+    for v in values:
+        fa, Zp, Bp = _cut(sh, v)
+        fa._pool = [None] * F
+        fa._pool_all = [None] * F if append_heldout else None
+        fa.M_a_ = [[None] * P for _ in range(F)]
+        fa.M_b_ = [[None] * P for _ in range(F)]
+        fa.canon_corrs_ = [[None] * P for _ in range(F)]
+        fa.maps_ = [[None] * P for _ in range(F)]
+        fa.fallbacks_ = []
+        fas.append(fa)
+        Zps.append(Zp)
+        Bps.append(Bp)
+    jobs = [(e, f) for e in range(len(values)) for f in range(F)]              # a job: fold f under value e
+    kj = {(e, f): fas[e].n_components_[f] for e, f in jobs}
+    per_job = [N * T * kj[j] * 8 + (pool_rows[j[1]] + held_rows[j[1]]) * T * kj[j] * 4 for j in jobs]
+    for chunk in _fold_chunks(per_job, max_bytes):
+        chunk = [jobs[i] for i in chunk]
         # 5: Z_f and the target rows of the pooled tensors
         Z, entries = {}, []
-        for f in chunk:
-            Z[f] = torch.empty(N * T, kf[f], dtype=LA.F64, device=Xd.device)
-            whole = torch.empty(pool_rows[f] + held_rows[f], T, kf[f], dtype=torch.float32, device=Xd.device)
+        for e, f in chunk:
+            fa, k = fas[e], kj[e, f]
+            Z[e, f] = torch.empty(N * T, k, dtype=LA.F64, device=Xd.device)
+            whole = torch.empty(pool_rows[f] + held_rows[f], T, k, dtype=torch.float32, device=Xd.device)
             fa._pool[f] = whole[:pool_rows[f]]
-            entries.append((X2, fa._mean_d[f], fa._W_d[f], Z[f]))
-            p2 = whole.view(-1, kf[f])
+            entries.append((X2, fa._mean_d[f], fa._W_d[f], Z[e, f]))
+            p2 = whole.view(-1, k)
             runs = plan.train_runs[f]
             if append_heldout:
                 fa._pool_all[f] = whole
@@ -306,23 +397,24 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
         LA.apply_grouped(entries)
         # 6: condition means of every fold
         A, segs = {}, []
-        for f in chunk:
-            nc = len(plan.cond_keys[f])
-            A[f] = torch.empty(nc, T, kf[f], dtype=LA.F64, device=Xd.device)
-            Zv = Z[f].view(N, T * kf[f])
+        for e, f in chunk:
+            nc, k = len(plan.cond_keys[f]), kj[e, f]
+            A[e, f] = torch.empty(nc, T, k, dtype=LA.F64, device=Xd.device)
+            Zv = Z[e, f].view(N, T * k)
             st, od = plan.cond_start[f], plan.cond_order[f]
-            segs += [(Zv, A[f][ci], od[st[ci]:st[ci + 1]]) for ci in range(nc)]
+            segs += [(Zv, A[e, f][ci], od[st[ci]:st[ci + 1]]) for ci in range(nc)]
         LA.cnd_avg_folds(segs)
         # 7: C_aa, C_bb, C_ab of every (fold, patient) with at least as many rows as columns
         probs, table = [], []
-        for f in chunk:
-            A2 = A[f].view(-1, kf[f])
+        for e, f in chunk:
+            k, Bp = kj[e, f], Bps[e]
+            A2 = A[e, f].view(-1, k)
             for p in range(P):
                 i_a, i_b = plan.shared[f][p]
                 rows = len(i_a) * T
-                pr = {'f': f, 'p': p, 'n': rows}
+                pr = {'e': e, 'f': f, 'p': p, 'n': rows}
                 probs.append(pr)
-                if rows < max(kf[f], Bp[p].shape[1]):
+                if rows < max(k, Bp[p].shape[1]):
                     pr['fallback'] = True
                     continue
                 ba, bb = i_a * T, i_b * T
@@ -334,23 +426,25 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
         for pr in probs:
             if pr.get('fallback'):
                 continue
+            k, dp = kj[pr['e'], pr['f']], Bps[pr['e']][pr['p']].shape[1]
             for name in ('Caa', 'Cbb', 'Cab'):
                 blk = out[offs[j]:offs[j + 1]]
                 j += 1
-                da = kf[pr['f']] if name != 'Cbb' else Bp[pr['p']].shape[1]
-                db = kf[pr['f']] if name == 'Caa' else Bp[pr['p']].shape[1]
+                da = k if name != 'Cbb' else dp
+                db = k if name == 'Caa' else dp
                 Cm, sa, sb = blk[:da * db].reshape(da, db), blk[da * db:da * db + da], blk[da * db + da:da * db + da + db]
                 Cm = Cm - np.outer(sa, sb) / blk[-1]
                 pr[name] = Cm if name == 'Cab' else 0.5 * (Cm + Cm.T)
         # 8: the d x d problems
         _solve_cca([pr for pr in probs if not pr.get('fallback')])
         for pr in probs:
-            f, p = pr['f'], pr['p']
+            e, f, p = pr['e'], pr['f'], pr['p']
+            fa, k, Bp = fas[e], kj[e, f], Bps[e]
             if pr.get('fallback'):
                 # rank-deficient or badly conditioned: the per-problem route on the same L matrices
                 i_a, i_b = plan.shared[f][p]
                 dev = Xd.device
-                La = A[f][torch.from_numpy(i_a).to(dev)].reshape(-1, kf[f])
+                La = A[e, f][torch.from_numpy(i_a).to(dev)].reshape(-1, k)
                 Lb = Bp[p].view(-1, T, Bp[p].shape[1])[torch.from_numpy(i_b).to(dev)].reshape(-1, Bp[p].shape[1])
                 pr['M_a'], pr['M_b'], pr['S'] = _cca_device(La, Lb)
                 pr['map'] = LA.dgemm(LA.to_device(pr['M_b']), LA.to_device(LA.pinv_small(pr['M_a']))).cpu().numpy()
@@ -360,12 +454,13 @@ def fit_folds(X, y_align, pool_data, splits, n_components=0.95, max_bytes=2 ** 3
         flat = LA.to_device(np.concatenate([np.ascontiguousarray(pr['map']).reshape(-1) for pr in probs])) if probs else None
         entries, o = [], 0
         for pr in probs:
-            f, p = pr['f'], pr['p']
-            dp = Bp[p].shape[1]
-            fa.maps_[f][p] = flat[o:o + dp * kf[f]].view(dp, kf[f])
-            o += dp * kf[f]
+            e, f, p = pr['e'], pr['f'], pr['p']
+            fa, k = fas[e], kj[e, f]
+            dp = Bps[e][p].shape[1]
+            fa.maps_[f][p] = flat[o:o + dp * k].view(dp, k)
+            o += dp * k
             r0 = (n_train[f] + sum(pool_n[:p])) * T
-            entries.append((Zp[p], None, fa.maps_[f][p], fa._pool[f].view(-1, kf[f])[r0:r0 + pool_n[p] * T]))
+            entries.append((Zps[e][p], None, fa.maps_[f][p], fa._pool[f].view(-1, k)[r0:r0 + pool_n[p] * T]))
         LA.apply_grouped(entries)
         del Z, A
-    return fa
+    return fas

@@ -144,7 +144,14 @@ def fit_many(Xs, n_components=None, solver='covariance'):
     what the separate fits give, bit for bit.  Only the covariance solver is batched."""
     if solver != 'covariance':
         raise ValueError(f"fit_many batches the covariance solver only; got solver={solver!r}")
-    models, means, covs, shapes = [], [], [], []
+    return [PCA(n_components=n_components, solver=solver)._fit_from_eig(e, mean, n, d) for e, mean, n, d in eig_many(Xs)]
+
+
+def eig_many(Xs):
+    """The part of ``fit_many`` that does not look at ``n_components``: per input (eig, mean, n, d) -- the eigendecomposition of its
+    covariance, its column mean (device) and its shape -- with ONE eigh_psd_batched call.  ``PCA(v)._fit_from_eig(eig, mean, n, d)``
+    is then the fit for any ``v``, so one decomposition serves a list of component counts (alignment.fit_folds_multi)."""
+    means, covs, shapes = [], [], []
     for x in Xs:
         Xd = LA.to_device(x)
         Xd = Xd.reshape(-1, Xd.shape[-1])
@@ -153,9 +160,8 @@ def fit_many(Xs, n_components=None, solver='covariance'):
         means.append(mean)
         covs.append(LA.xcov(Xd, None, mean) / (n - 1))
         shapes.append((n, d))
-        models.append(PCA(n_components=n_components, solver=solver))
-    eigs = LA.eigh_psd_batched(covs) if covs else []
-    return [m._fit_from_eig(e, mean, n, d) for m, e, mean, (n, d) in zip(models, eigs, means, shapes)]
+    eigs = list(LA.eigh_psd_batched(covs)) if covs else []
+    return [(e, mean, n, d) for e, mean, (n, d) in zip(eigs, means, shapes)]
 
 
 class GramPCA(PCA):

@@ -4,3 +4,4 @@ from .svm import SVC  # noqa: F401,E402
 from .bagging import BaggingClassifier  # noqa: F401,E402
 from .search import SVCSearchCV  # noqa: F401,E402
 from .fold_decode import FoldDecode, cross_val_decode  # noqa: F401,E402
+from .aligned_search import AlignedSVCSearchCV  # noqa: F401,E402

@@ -851,7 +851,36 @@ int xps_svm_cv_score_f64(const double* K, const int64_t* mbase, const int64_t* m
                          const int* npos, const double* alpha, const double* rho, const int* pair_a, const int* pair_b,
                          const int* mod_off, const int* tst, const int* ytrue, const int* tst_off, int S, int k, int* pred, int* conf,
                          double* dec_out, int64_t ldd, void* ws, size_t ws_bytes, void* stream);
-/* small dense float64 GEMM  C = op(A) op(B)  (row-major, op = transpose flag) */
+/* The ragged kernels of the search through the aligned decoder (decoders/aligned_search.py; BayesSearchCV over a
+ * crossPtDecoder_sepAlign, scripts/aligned_decode_svm_ncv.py:388-413): the kernel matrices of all (alignment, fold, gamma) and the
+ * 'scale' variances of all (alignment, fold) in one launch each, however many candidates are searched.  Both follow
+ * xps_gram_grouped_f64's convention: HOST tables, checked by the call and copied into ws (DEVICE, ..._workspace(...) bytes) on the
+ * stream; they must stay valid until the stream has passed the call.  Nothing synchronises.
+ *
+ * xps_rbf_grouped_from_gram_f64: n_problems rbf maps of square Gram matrices.  Words of a problem (XPS_RBF_GROUPED_WORDS each):
+ * 0 G (float64 n x n), 1 ldg (>= n), 2 n, 3 gamma (the bits of a double, finite and >= 0), 4 K (float64 n x n), 5 ldk (>= n).
+ *   K_p[i][j] = exp(-gamma_p (G_p[i][i] + G_p[j][j] - 2 G_p[i][j])):
+ * xps_rbf_from_gram_f64's bits for na = nb = the diagonal of G_p.  Several problems may read one G with different gammas; a K may
+ * not be a G of the call (K == G of its own problem is refused, the rest is the caller's).  tiles: int32[3 * n_tiles] =
+ * {problem, 64-row tile ti, 64-column tile tj} for every tile of every problem; one workgroup per tile, no atomics, the result does
+ * not depend on the grid.  Elements of K_p beyond column n of a row are not written; a problem with n = 0 has no tiles and writes
+ * nothing.  Refused with XPS_E_INVALID before any launch: null tables or matrices, negative counts, ldg < n, ldk < n, a negative or
+ * non-finite gamma, a tile that names no problem or starts at or past n, a null or too small workspace.
+ *
+ * xps_var_grouped_f64: out[e] (float64, DEVICE, n_entries elements) = the population variance of all elements of entry e's row
+ * block: the mean of the squared deviations from the mean of its rows * D elements (numpy's X.var(); 0 for an empty block).  Words
+ * of an entry (XPS_VAR_GROUPED_WORDS each): 0 V (row-major float32 or float64), 1 v_is_f32, 2 ldv (>= D), 3 first row, 4 rows, 5 D.
+ * One workgroup per entry; two passes in float64 (the mean, then the deviations); a thread adds its elements in ascending order
+ * and the partial sums meet in a fixed tree: no atomics, two runs give the same bits.  Refused with XPS_E_INVALID before any
+ * launch: a null table, output or matrix, negative counts, ldv < D, v_is_f32 outside 0 / 1, a null or too small workspace. */
+#define XPS_RBF_GROUPED_WORDS 8
+size_t xps_rbf_grouped_from_gram_f64_workspace(int n_problems, int n_tiles);
+int xps_rbf_grouped_from_gram_f64(const int64_t* problems, int n_problems, const int32_t* tiles, int n_tiles, void* ws,
+                                  size_t ws_bytes, void* stream);
+#define XPS_VAR_GROUPED_WORDS 8
+size_t xps_var_grouped_f64_workspace(int n_entries);
+int xps_var_grouped_f64(const int64_t* entries, int n_entries, double* out, void* ws, size_t ws_bytes, void* stream);
+/* small dense float64 GEMM C = op(A) op(B)  (row-major, op = transpose flag) */
 int xps_dgemm_small(const double* A, int64_t lda, int ta, const double* B, int64_t ldb, int tb,
                     double* C, int64_t ldc, int M, int N, int K, void* stream);
 /* the same product with the contraction split over workgroups (few output tiles, long K: the skinny products of the MCCA
