@@ -423,6 +423,15 @@ int xps_ctc_collapse_f32(const float* logits, int n_classes, int blank, int64_t*
  *   logits [B][n_classes] (always from_logits).  state: ..._state_bytes(B, beam_size, max_steps) bytes, one
  *   block per stream starting with int32 {step, n_members, overflow, 0}; all zero = the empty beam (the caller's reset).
  *   A step with step == max_steps sets the sticky overflow flag and leaves the beam as it is.  Graph-capturable.
+ *   Layout of one stream block (tests/ctc_beam_state.py decodes it):
+ *     header, 64 bytes: int32 {step, n_members, overflow, 0};
+ *     member set, beam_size * 68 bytes rounded up to a multiple of 64, K = beam_size: double p_b[K], p_nb[K];
+ *       uint64 h1[K], h2[K] (hashes of the prefix), hp1[K], hp2[K] (of the prefix without its last token), cmask[K]
+ *       (bit t: prefix + (t,) is a member); int32 len[K], last[K] (-1 for the empty prefix), parent[K] (the rank of the
+ *       prefix without its last token, or -1).  Ranks >= n_members and the padding are unspecified;
+ *     backpointers: int32 hist[max_steps][K], hist[t][r] = rank in the previous frame | (appended token + 1) << 16 for
+ *       the member of rank r after frame t; ranks >= that frame's member count and frames >= step are not written;
+ *     the block's stride is rounded up to a multiple of 256 bytes.
  * ..._readout: stream s's best prefix so far into prefix [max_steps] int64, its length and nll (one each). */
 size_t xps_ctc_beam_workspace(int B, int T, int beam_size, int n_classes);
 int xps_ctc_beam_f64(const void* log_probs, int is_f32, int B, int T, int n_classes, const int64_t* input_lengths,
