@@ -12,6 +12,7 @@ start state, and ``patient`` says which trial is whose.  There is no CPU fallbac
 import numpy as np
 import torch
 
+from .ctc_align import forced_align
 from .ctc_decoder import _beam_device, check_beam_sizes, greedy_decode_device
 from .realtime_nn_model import per_device
 from .realtime_processing import _check_trials, _good_mask, _hg_trials, _split_coefs, _trial_lengths, _trials_on_device
@@ -23,11 +24,18 @@ class SessionResult:
     """What SessionReplay.run returns (device tensors): logits (N, n_pred, n_classes) float32; tokens (N, n_pred) int64,
     the decoded labels of each trial, then -1; token_lengths (N,) int64; pred_lengths (N,) int64, the valid predictions
     of each trial; features (N, n_bins, d) float32; beam_nll (N,) float64 with decoder='beam', else None; per, a 0-dim
-    float64 tensor, when targets were given, else None."""
+    float64 tensor, when targets were given, else None; blank, the model's blank label (align needs it)."""
 
-    def __init__(self, logits, tokens, token_lengths, pred_lengths, features, beam_nll=None, per=None):
+    def __init__(self, logits, tokens, token_lengths, pred_lengths, features, beam_nll=None, per=None, blank=0):
         self.logits, self.tokens, self.token_lengths, self.pred_lengths = logits, tokens, token_lengths, pred_lengths
         self.features, self.beam_nll, self.per = features, beam_nll, per
+        self.blank = blank
+
+    def align(self, targets, target_lengths=None):
+        """Forced alignment (realtime_sim/ctc_align.py) of each trial's known targets through the log-softmax of its logits,
+        over the trial's pred_lengths valid predictions -> CTCAlignment; frame w is prediction w."""
+        return forced_align(torch.log_softmax(self.logits, dim=2), targets, input_lengths=self.pred_lengths,
+                            target_lengths=target_lengths, blank=self.blank)
 
     def decoded(self):
         """The tokens as a list of 1-D LongTensors (one transfer of the N lengths)."""
@@ -200,4 +208,4 @@ class SessionReplay:
             if target_lengths is None:
                 raise ValueError('targets need target_lengths')
             per = per_device(tokens, token_lengths, torch.as_tensor(targets).to(self.dev), target_lengths)
-        return SessionResult(logits, tokens, token_lengths, pred_lengths, feats, beam_nll, per)
+        return SessionResult(logits, tokens, token_lengths, pred_lengths, feats, beam_nll, per, self.blank)

@@ -443,6 +443,34 @@ int xps_ctc_beam_step_f32(const float* logits, int n_classes, int blank, int bea
 int xps_ctc_beam_readout(const void* state, size_t state_bytes, int B, int beam_size, int max_steps, int s,
                          int64_t* prefix, int64_t* prefix_len, double* nll, void* stream);
 
+/* CTC forced alignment (realtime_sim/ctc_align.py): the Viterbi best path of a KNOWN target through the
+ * frame scores, one launch for the batch, one 64-lane workgroup per sequence, no host synchronisation.
+ * scores: float32 (is_f32 = 1) or float64, any per-frame scores (no softmax is applied: with log-probabilities the path
+ *   score is the path's log-probability); frame t of sequence b starts at element t * stride_t + b * stride_b, its C
+ *   classes are contiguous -- (T, B, C) and (B, T, C) tensors and permuted views of them are read in place.
+ * targets [B][target_stride] int64, max_target_len = Lmax <= target_stride; input_lengths / target_lengths [B] int64, NULL:
+ *   all T / all Lmax.  Lengths are clamped to 0..T / 0..Lmax and labels to 0..C-1 for memory safety only.
+ * Recursion, float64 additions and comparisons only.  Tb and L the lengths of a sequence, extended label
+ *   l' = (blank, l_1, blank, ..., l_L, blank), S = 2 L + 1 states, x_t(c) the score widened to float64:
+ *     v_0(0) = x_0(blank), v_0(1) = x_0(l_1), every other state -inf;
+ *     v_t(s) = x_t(l'_s) + max(v_{t-1}(s), v_{t-1}(s-1), [s odd, s >= 3 and l'_s != l'_{s-2}] v_{t-1}(s-2)).
+ * TIE RULE (part of the contract): among the predecessors the first of (stay, s-1, s-2) that attains the maximum wins, so
+ *   a move needs a strictly larger value; the path ends in state S-1 unless v_{Tb-1}(S-2) is strictly larger.
+ * Outputs: states [B][T] int32, the extended-state index of each frame, -1 from frame Tb on; token_start / token_end
+ *   [B][Lmax] int32, the first frame and one past the last frame spent in state 2 j + 1, -1 for j >= L; path_score [B]
+ *   float64 = v_{Tb-1}(end state).  A path score of -inf is INFEASIBLE (fewer frames than L + the number of adjacent equal
+ *   labels, or every path crosses a -inf score): all states and spans -1.  Tb = 0: score 0 for L = 0, else infeasible.
+ *   L = 0: the all-blank path.  NaN or +inf scores: an unspecified path, no out-of-range access.
+ * Workspace: ..._workspace bytes, one backpointer byte per (b, t, s) at (b * T + t) * (2 Lmax + 1) + s; only 1 <= t < Tb,
+ *   s < S are written.
+ * XPS_E_INVALID before any launch: a negative size or stride, C < 1, blank outside 0..C-1, 2 Lmax + 1 > 1023 (the CTC
+ *   loss's state cap), target_stride < Lmax, a NULL pointer that the sizes need, a workspace smaller than ..._workspace. */
+size_t xps_ctc_align_workspace(int B, int T, int max_target_len);
+int xps_ctc_align(const void* scores, int is_f32, int64_t stride_t, int64_t stride_b, int T, int B, int C,
+                  int max_target_len, const int64_t* targets, int64_t target_stride, const int64_t* input_lengths,
+                  const int64_t* target_lengths, int blank, int32_t* states, int32_t* token_start, int32_t* token_end,
+                  double* path_score, void* workspace, size_t workspace_bytes, void* stream);
+
 /* out[b][:] = table[idx[b]][:]  (embedding / precomputed input projection rows) */
 int xps_gather_rows_f32(const float* table, const int64_t* idx, float* out,
                         int B, int cols, int n_rows, void* stream);
