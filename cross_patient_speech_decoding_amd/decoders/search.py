@@ -47,6 +47,14 @@ BATCHED = ('C', 'gamma')                    # the SVC parameters that are batche
 SCORINGS = (None, 'accuracy', 'balanced_accuracy')
 
 
+def check_class_count(k):
+    """The class counts every cross-validated driver takes: sklearn's refusal of one class, the scoring kernel's of more than 64."""
+    if k < 2:
+        raise ValueError('The number of classes has to be greater than one; got 1 class')
+    if k > 64:
+        raise ValueError(f'the scoring kernel takes 2..64 classes; got {k}')
+
+
 # ------------------------------------------------------------------------------------------------ candidates (host)
 def expand_candidates(param_grid, candidates):
     """The list of candidate dicts: ``ParameterGrid(param_grid)`` in its order, or the explicit ``candidates`` as given."""
@@ -451,7 +459,39 @@ def _run_chunk(plan, mats, kernel, tol, svc_max_iter, k):
     return (models,) + solve_and_score(Kbuf, models, mn, mbase, tol, svc_max_iter, k)
 
 
-class SVCSearchCV(BaseEstimator):
+class SearchTail:
+    """What a fitted search is, whatever it searched: the ``scoring`` refusal, sklearn's result attributes from the confusion
+    tables, and ``predict`` / ``score`` through the refitted ``best_estimator_`` (each class refits in its own ``fit``)."""
+
+    def _check_scoring(self):
+        if self.scoring not in SCORINGS:
+            raise ValueError(f"scoring must be None, 'accuracy' or 'balanced_accuracy'; got {self.scoring!r}")
+
+    def _set_results(self, candidates, conf, test_predictions, classes):
+        """conf (n_candidates, n_splits, k, k), rows = true class; test_predictions: per split (test_idx, labels (n_candidates,
+        len(test_idx)))."""
+        self.cv_results_ = assemble_results(candidates, scores_from_confusion(conf, self.scoring))
+        self.cv_confusion_ = conf
+        self.cv_test_predictions_ = test_predictions
+        self.n_splits_ = conf.shape[1]
+        self.classes_ = classes
+        self.best_index_ = int(self.cv_results_['rank_test_score'].argmin())
+        self.best_params_ = self.cv_results_['params'][self.best_index_]
+        self.best_score_ = float(self.cv_results_['mean_test_score'][self.best_index_])
+
+    def _best(self):
+        if not hasattr(self, 'best_estimator_'):
+            raise AttributeError(f'this {type(self).__name__} has no best_estimator_: it was not fitted, or refit=False')
+        return self.best_estimator_
+
+    def predict(self, X):
+        return self._best().predict(X)
+
+    def score(self, X, y):
+        return self._best().score(X, y)
+
+
+class SVCSearchCV(SearchTail, BaseEstimator):
     """``GridSearchCV`` for ``decoders.SVC`` (bare, or the last step of a sklearn ``Pipeline``) with all folds and all ``C`` /
     ``gamma`` candidates trained and scored as one device problem per chunk.
 
@@ -489,8 +529,7 @@ class SVCSearchCV(BaseEstimator):
     def _check_settings(self):
         svc, _, _ = svc_of(self.estimator)
         svc._check_settings()
-        if self.scoring not in SCORINGS:
-            raise ValueError(f"scoring must be None, 'accuracy' or 'balanced_accuracy'; got {self.scoring!r}")
+        self._check_scoring()
         if self.return_train_score:
             raise NotImplementedError('return_train_score is not implemented on the HIP path')
         if not (isinstance(self.error_score, float) and np.isnan(self.error_score)):
@@ -508,10 +547,7 @@ class SVCSearchCV(BaseEstimator):
             raise ValueError('X must have one row per element of y (n_samples,)')
         classes, yi = np.unique(y, return_inverse=True)
         k = len(classes)
-        if k < 2:
-            raise ValueError('The number of classes has to be greater than one; got 1 class')
-        if k > 64:
-            raise ValueError(f'the scoring kernel takes 2..64 classes; got {k}')
+        check_class_count(k)
         cv = check_cv(self.cv, y, classifier=True)
         splits = [(np.asarray(tr), np.asarray(te)) for tr, te in cv.split(X, y)]
         if not splits:
@@ -525,32 +561,12 @@ class SVCSearchCV(BaseEstimator):
             for s, mod in enumerate(models):
                 conf[mod['cand'], mod['fold']] = conf_c[s]
                 labels[mod['fold']][mod['cand']] = classes[pred_c[tst_off[s]:tst_off[s + 1]]]
-        scores = scores_from_confusion(conf, self.scoring)
-        self.cv_results_ = assemble_results(candidates, scores)
-        self.cv_confusion_ = conf
+        self._set_results(candidates, conf, [(te, lab) for (_, te), lab in zip(splits, labels)], classes)
         if self.batch_pca:
             self.pca_n_components_, self.pca_fallbacks_ = plan.pca['n_components'], plan.pca['fallbacks']
-        self.cv_test_predictions_ = [(te, lab) for (_, te), lab in zip(splits, labels)]
-        self.n_splits_ = len(splits)
-        self.classes_ = classes
-        self.best_index_ = int(self.cv_results_['rank_test_score'].argmin())
-        self.best_params_ = self.cv_results_['params'][self.best_index_]
-        self.best_score_ = float(self.cv_results_['mean_test_score'][self.best_index_])
         if self.refit:
             self.best_estimator_ = clone(self.estimator).set_params(**self.best_params_).fit(X, y)
         return self
 
-    # ------------------------------------------------------------------ the refitted estimator
-    def _best(self):
-        if not hasattr(self, 'best_estimator_'):
-            raise AttributeError('this SVCSearchCV has no best_estimator_: it was not fitted, or refit=False')
-        return self.best_estimator_
-
-    def predict(self, X):
-        return self._best().predict(X)
-
     def decision_function(self, X):
         return self._best().decision_function(X)
-
-    def score(self, X, y):
-        return self._best().score(X, y)

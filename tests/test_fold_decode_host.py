@@ -1,6 +1,7 @@
 """decoders.cross_val_decode, the host side (no GPU): the partition cutter, the (fold, estimator) problem builder against a per-fold
 restatement of SVC.fit's / BaggingClassifier.fit's construction, the host vote against a numpy restatement, the scores against
-sklearn.metrics, and every refusal."""
+sklearn.metrics, every refusal (those of the front matter through both entry points that share it), and the one-candidate plan
+cross_val_decode hands the partition engine."""
 import numpy as np
 import pytest
 from sklearn.decomposition import PCA as SkPCA
@@ -248,6 +249,63 @@ def test_pipelines_and_unsupported_settings_are_not_implemented():
         D.cross_val_decode(D.crossPtDecoder_sepAlign(_pool(), D.BaggingClassifier(D.SVC(), oob_score=True), AlignCCA), X, y)
     with pytest.raises(ValueError, match='n_trials'):
         D.cross_val_decode(D.crossPtDecoder_sepAlign(_pool(), D.SVC(), AlignCCA), X, np.stack([y, y], axis=1))
+
+
+def _one_class_pool():
+    return [(np.zeros((12, 4, 6)), np.zeros(12, dtype=int), np.zeros(12, dtype=int))]
+
+
+@pytest.mark.parametrize('pool, y, message', [
+    (_pool(), np.stack([np.arange(12) % 3] * 2, axis=1), r'^y must be \(n_trials,\)$'),
+    (_one_class_pool(), np.zeros(12, dtype=int), '^The number of classes has to be greater than one; got 1 class$'),
+    (_pool(), np.arange(130) % 65, r'^the scoring kernel takes 2\.\.64 classes; got 65$'),
+], ids=['2-D y', 'one class', '65 classes'])
+def test_both_entry_points_refuse_the_same_things_with_the_same_messages(pool, y, message):
+    """The one front matter (``decode_setup``, ``search.check_class_count``), before anything touches the device."""
+    X = np.zeros((len(y), 4, 5))
+    model = D.crossPtDecoder_sepAlign(pool, D.SVC(), AlignCCA)
+    with pytest.raises(ValueError, match=message):
+        D.cross_val_decode(model, X, y)
+    with pytest.raises(ValueError, match=message):
+        D.AlignedSVCSearchCV(model, {'n_comp': [3]}).fit(X, y)
+    with pytest.raises(ValueError, match=message):
+        FD.decode_setup(model, y, None, 5)
+
+
+def test_the_front_matter_of_a_run():
+    y = np.array([5, 3, 7] * 4)
+    pool = [(np.zeros((4, 4, 6)), np.array([3, 11, 3, 5]), None)]
+    model = D.crossPtDecoder_sepAlign(pool, D.SVC(), AlignCCA)
+    y_out, y_al, pool_out, classes, yi_tar, yi_pool, parts = FD.decode_setup(model, list(y), None, StratifiedKFold(3))
+    assert np.array_equal(y_out, y) and y_al is y_out and len(pool_out) == 1
+    assert classes.tolist() == [3, 5, 7, 11]                                      # the union: the target never shows 11
+    assert yi_tar.dtype == np.int32 and np.array_equal(classes[yi_tar], y)
+    assert yi_pool.dtype == np.int32 and yi_pool.tolist() == [0, 3, 0, 1]
+    assert [len(p) for p in parts] == [3]
+    marker = object()
+    assert FD.decode_setup(model, y, marker, StratifiedKFold(3))[1] is marker
+    assert len(FD.decode_setup(model, y, None, RepeatedStratifiedKFold(n_splits=2, n_repeats=3, random_state=0))[6]) == 3
+
+
+# ------------------------------------------------------------------------------------------------ the one-candidate plan
+@pytest.mark.parametrize('kernel, gamma', [('rbf', 'scale'), ('rbf', 0.25), ('linear', 'scale')], ids=['rbf-scale', 'rbf-float', 'linear'])
+def test_one_candidate_is_one_view_one_matrix_and_one_model_per_fold(kernel, gamma):
+    """What cross_val_decode hands the engine: one setting on one alignment."""
+    settings = [dict(C=2.0, gamma=FD.gamma_spec(kernel, gamma))]
+    rows = [225, 226, 225, 224]
+    plan = FD.build_plan(settings, [0], [rows], kernel, lambda a, f, spec: 0.5 + f if spec == 'scale' else spec)
+    value = {('rbf', 'scale'): lambda f: 0.5 + f, ('rbf', 0.25): lambda f: 0.25, ('linear', 'scale'): lambda f: None}[kernel, gamma]
+    assert plan.views == [(0, f) for f in range(4)] and plan.rows == rows
+    assert plan.matrices == [(f, value(f)) for f in range(4)]
+    assert plan.models == [dict(cand=0, fold=f, view=f, matrix=f, C=2.0) for f in range(4)]
+    assert plan.matrix_bytes() == [8 * n ** 2 for n in rows]
+    assert FD.scale_views(settings, [0], 4, kernel) == ([(0, f) for f in range(4)] if (kernel, gamma) == ('rbf', 'scale') else [])
+    rbf = kernel == 'rbf'
+    assert FD.cut_plan_chunks(plan, rbf, 2 ** 30) == [[0, 1, 2, 3]]
+    assert FD.cut_plan_chunks(plan, rbf, 8 * 226 ** 2) == [[0], [1], [2], [3]]    # for rbf each with its Gram beside it
+    assert len(FD.cut_plan_chunks(plan, rbf, 2 * 8 * 226 ** 2)) == (4 if rbf else 2)
+    with pytest.raises(ValueError, match='too small'):
+        FD.cut_plan_chunks(plan, rbf, 8 * 226 ** 2 - 1)
 
 
 def test_supported_models_pass_the_check():

@@ -10,8 +10,8 @@ held-out row whose libsvm one-vs-one decisions all have magnitude >= 1e-3 (the p
 candidate's rows may be left out by that rule (a condition on the data, not a tolerance: with the reference path alone the worst
 candidate of these grids leaves out 3 of 72 rows in case A and 5 of 90 in case B).
 
-Against ``cross_val_decode`` on the same candidate the search is exact on every row: same Gram bits, same rbf expression, same
-deterministic SMO."""
+Against ``cross_val_decode`` on the same candidate -- the same engine with that candidate alone -- the search is exact on every row:
+same Gram bits, same rbf expression, same deterministic SMO."""
 import functools
 import sys
 from collections import Counter
@@ -182,7 +182,11 @@ def test_every_candidate_predicts_what_libsvm_predicts(name, kernel):
     assert max(ref_scores) - min(ref_scores) > 0.1
 
 
-# ------------------------------------------------------------------------------------------------ the existing device path
+# ------------------------------------------------------------------------------------------------ candidates side by side and alone
+# cross_val_decode is the one-candidate case of the engine the search runs (fold_decode.run_partition), so these two tests check that a
+# candidate among others -- sharing an alignment, a Gram matrix or a kernel matrix with them -- gets exactly what it gets alone.  The
+# independent references are libsvm on the CPU (above; tests/test_gpu_fold_decode.py for cross_val_decode itself) and, for the bagged
+# model, the per-fold device loop of tests/test_gpu_fold_decode.py.
 def _check_against_cross_val_decode(search, model, name):
     X, y, yfull, _, _ = _inputs(name)
     for c, cand in enumerate(search.cv_results_['params']):
@@ -294,14 +298,14 @@ def test_the_launch_count_does_not_depend_on_the_number_of_candidates(monkeypatc
 
 
 def test_every_chunking_gives_the_same_results_with_one_launch_of_each_kernel_per_chunk(monkeypatch):
-    from cross_patient_speech_decoding_amd.decoders import aligned_search as AS
+    from cross_patient_speech_decoding_amd.decoders import fold_decode as FD
     whole = _search('A', 'rbf')
     X, y, yfull, _, _ = _inputs('A')
     largest = 8 * max(len(tr) + len(te) + sum(len(x) for x, _, _ in _inputs('A')[3]) for tr, te in _splits('A')) ** 2
     counts = _count_calls(monkeypatch)
     chunks = []
-    real = AS.cut_plan_chunks
-    monkeypatch.setattr(AS, 'cut_plan_chunks', lambda *a: chunks.append(real(*a)) or chunks[-1])
+    real = FD.cut_plan_chunks
+    monkeypatch.setattr(FD, 'cut_plan_chunks', lambda *a: chunks.append(real(*a)) or chunks[-1])
     for limit in (8 * largest, 2 * largest):
         counts.clear()
         cut = D().AlignedSVCSearchCV(_model('A', 'rbf'), GRIDS['rbf'], cv=_cv('A'), refit=False, max_kernel_bytes=limit).fit(X, y, y_align=yfull)

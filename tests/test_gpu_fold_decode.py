@@ -202,17 +202,30 @@ def _same(a, b):
 
 
 @pytest.mark.parametrize('which', ['bagged', 'rbf'])
-def test_two_runs_and_every_chunking_give_the_same_bits(which):
+def test_two_runs_and_every_chunking_give_the_same_bits(which, monkeypatch):
+    from cross_patient_speech_decoding_amd.decoders import fold_decode as FD
+    from cross_patient_speech_decoding_amd.decoders.search import cut_chunks
     X, y, yfull, _, folds = _inputs('A')
-    model = _bagged('A') if which == 'bagged' else _model('A', _svc('rbf'))
+    rbf = which == 'rbf'
+    model = _model('A', _svc('rbf')) if rbf else _bagged('A')
     cv = StratifiedKFold(folds, shuffle=True, random_state=0)
+    cuts, real = [], FD.cut_plan_chunks                                  # what the engine cut, call by call
+    monkeypatch.setattr(FD, 'cut_plan_chunks', lambda *args: cuts.append(real(*args)) or cuts[-1])
     a = D().cross_val_decode(model, X, y, y_align=yfull, cv=cv)
     assert _same(a, D().cross_val_decode(model, X, y, y_align=yfull, cv=cv))
-    per_fold = [8 * a.alignment_[0].pool_with_heldout(f)[0].shape[0] ** 2 for f in range(folds)]
-    from cross_patient_speech_decoding_amd.decoders.search import cut_chunks
-    for max_bytes, chunks in ((2 * max(per_fold), 2), (max(per_fold), folds)):
-        assert len(cut_chunks(per_fold, max_bytes)) == chunks and len(cut_chunks(per_fold, 2 ** 30)) == 1
+    rows = [a.alignment_[0].pool_with_heldout(f)[0].shape[0] for f in range(folds)]
+    per_fold = [8 * n ** 2 for n in rows]
+    assert len(cut_chunks(per_fold, 2 ** 30)) == 1 and [len(c) for c in cuts] == [1, 1]
+    # the engine's own rule on a one-candidate plan: a chunk holds its kernel matrices and, for rbf, the Gram matrix of each of their
+    # views -- with one candidate a second matrix per fold, so the limits that hold 4, 2 and 1 linear folds hold 2, 1 and 1 rbf folds
+    plan = FD.build_plan([dict(C=1.0, gamma=1.0 if rbf else None)], [0], [rows], 'rbf' if rbf else 'linear', lambda al, f, spec: spec)
+    for max_bytes, chunks in ((4 * max(per_fold), 2 if rbf else 1), (2 * max(per_fold), folds if rbf else 2), (max(per_fold), folds)):
+        assert len(cut_chunks(per_fold, max_bytes)) == {4: 1, 2: 2, 1: folds}[max_bytes // max(per_fold)]
+        assert len(real(plan, rbf, max_bytes)) == chunks
         assert _same(a, D().cross_val_decode(model, X, y, y_align=yfull, cv=cv, max_bytes=max_bytes))
+        assert len(cuts[-1]) == chunks and [m for ch in cuts[-1] for m in ch] == list(range(folds))
+        if rbf and max_bytes == max(per_fold):                           # F chunks, each one matrix plus its Gram
+            assert all(FD.chunk_bytes(plan, ch, True) == 2 * max(per_fold) for ch in cuts[-1])
     with pytest.raises(ValueError, match='too small'):
         D().cross_val_decode(model, X, y, y_align=yfull, cv=cv, max_bytes=max(per_fold) - 1)
 
@@ -231,12 +244,16 @@ def test_one_launch_of_each_kernel_for_all_folds_and_estimators(monkeypatch):
             monkeypatch.setattr(mod, 'call', counting)
     X, y, yfull, _, folds = _inputs('A')
     cv = StratifiedKFold(folds, shuffle=True, random_state=0)
-    for model, rbf in ((_bagged('A'), 0), (_model('A', _svc('linear')), 0), (_model('A', _svc('rbf')), folds)):
+    # (model, rbf map launches, variance launches): gamma='scale' is the SVC's default; a float gamma needs no variance
+    for model, rbf, var in ((_bagged('A'), 0, 0), (_model('A', _svc('linear')), 0, 0), (_model('A', _svc('rbf')), 1, 1),
+                            (_model('A', D().SVC(kernel='rbf', gamma=1e-4, class_weight='balanced', tol=TOL)), 1, 0)):
         counts.clear()
         D().cross_val_decode(model, X, y, y_align=yfull, cv=cv)
         print(dict(counts))
         for entry in ('xps_gram_grouped_f64', 'xps_svm_smo_multi_f64', 'xps_svm_cv_score_f64'):
             assert counts[entry] == 1, (entry, dict(counts))
-        assert counts['xps_rbf_from_gram_f64'] == rbf, dict(counts)
+        assert counts['xps_rbf_grouped_from_gram_f64'] == rbf, dict(counts)     # ONE launch for the F folds
+        assert counts['xps_var_grouped_f64'] == var, dict(counts)
+        assert counts['xps_rbf_from_gram_f64'] == 0, dict(counts)
         for entry in ('xps_svm_smo_f64', 'xps_bag_vote_f64', 'xps_bag_coef_scatter_f64', 'xps_rbf_multi_from_gram_f64'):
             assert counts[entry] == 0, (entry, dict(counts))

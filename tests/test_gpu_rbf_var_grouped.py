@@ -61,7 +61,7 @@ def rbf_entry(tab, n_problems, tiles, n_tiles, ws=None, ws_bytes=None):
 
 
 def single(G_d, n, ldg, gamma):
-    """xps_rbf_from_gram_f64 on the same G with the diagonal as norms (what fold_decode._run_chunk does per fold)."""
+    """xps_rbf_from_gram_f64 on the same G with the diagonal as norms (the one-problem entry: the reference for the grouped entry's bits)."""
     torch = torch_()
     from cross_patient_speech_decoding_amd import _dev
     from cross_patient_speech_decoding_amd._lib import call

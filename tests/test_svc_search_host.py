@@ -78,6 +78,38 @@ def test_unknown_keys_wrong_estimators_and_unsupported_settings_are_refused():
         SVCSearchCV(SVC(), {'C': [1], 'tol': [1e-3]}).fit(X, y)
 
 
+def test_both_searches_share_one_tail():
+    """``search.SearchTail``: the same ``scoring`` refusal, the ``AttributeError`` naming the concrete class, ``decision_function``
+    on ``SVCSearchCV`` alone, and the class-count refusals of ``check_class_count``."""
+    from cross_patient_speech_decoding_amd.alignment import AlignCCA
+    from cross_patient_speech_decoding_amd.decoders import AlignedSVCSearchCV, crossPtDecoder_sepAlign
+    pool = [(np.zeros((9, 4, 6)), np.arange(9) % 3, np.arange(9) % 3)]
+    plain = SVCSearchCV(SVC(), {'C': [1]}, scoring='f1', refit=False)
+    aligned = AlignedSVCSearchCV(crossPtDecoder_sepAlign(pool, SVC(), AlignCCA), {'n_comp': [3]}, scoring='f1', refit=False)
+    assert isinstance(plain, S.SearchTail) and isinstance(aligned, S.SearchTail)
+    assert type(plain).predict is type(aligned).predict is S.SearchTail.predict and type(plain).score is type(aligned).score
+    message = r"^scoring must be None, 'accuracy' or 'balanced_accuracy'; got 'f1'$"
+    with pytest.raises(ValueError, match=message):
+        plain.fit(np.zeros((6, 2)), np.array([0, 1] * 3))
+    with pytest.raises(ValueError, match=message):
+        aligned.fit(np.zeros((12, 4, 5)), np.arange(12) % 3)
+    for search, X in ((plain, np.zeros((2, 2))), (aligned, np.zeros((2, 4, 5)))):
+        name = type(search).__name__
+        for use in (lambda: search.predict(X), lambda: search.score(X, [0, 1])):
+            with pytest.raises(AttributeError, match=f'^this {name} has no best_estimator_: it was not fitted, or refit=False$'):
+                use()
+    with pytest.raises(AttributeError, match='^this SVCSearchCV has no best_estimator_'):
+        plain.decision_function(np.zeros((2, 2)))
+    assert not hasattr(aligned, 'decision_function')
+    with pytest.raises(ValueError, match='^The number of classes has to be greater than one; got 1 class$'):
+        S.check_class_count(1)
+    with pytest.raises(ValueError, match=r'^the scoring kernel takes 2\.\.64 classes; got 65$'):
+        S.check_class_count(65)
+    assert S.check_class_count(2) is None and S.check_class_count(64) is None
+    with pytest.raises(ValueError, match=r'^the scoring kernel takes 2\.\.64 classes; got 65$'):
+        SVCSearchCV(SVC(), {'C': [1]}).fit(np.zeros((130, 2)), np.arange(130) % 65)
+
+
 # ------------------------------------------------------------------------------------------------ the problem builder
 def svc_fit_construction(svc, X, y):
     """What decoders.SVC.fit builds from the X / y it is handed (no sample weights): the lines of its fit, restated."""
