@@ -6,3 +6,5 @@ from .JointPCA import JointPCA  # noqa: F401
 from .alignment_utils import cnd_avg, extract_group_conditions, label2str  # noqa: F401
 from .pca import PCA, GramPCA, PCA_SPECTRUM_LIMIT, fit_many  # noqa: F401
 from .fold_align import FoldAlignment, fit_folds, fit_folds_multi, fold_plan  # noqa: F401
+from . import metrics  # noqa: F401
+from .metrics import ClusterScores, cluster_scores, pt_corr, pt_corr_multi  # noqa: F401

@@ -1080,3 +1080,104 @@ def svd_batched(Ks):
     Wb = to_device(np.ascontiguousarray(Ks.transpose(0, 2, 1)))         # [b] row j = column j of K[b]
     Vb = jacobi_batched(Wb, want_v=True)
     return [_svd_tail(W, V) for W, V in zip(Wb.cpu().numpy(), Vb.cpu().numpy())]
+
+
+# ------------------------------------------------------------------------------------ label-grouped sums (csrc/xps_cluster.hip)
+CLUSTER_MAX_CLASSES = 64                                     # XPS_CLUSTER_MAX_CLASSES of include/xps.h
+
+
+def _check_label_sets(labels_t, k, what):
+    """(n, R) of the transposed label array of a call: labels_t[j][r] uint8 on the device, contiguous; 2 <= k <= 64.  The values
+    are the caller's to check before the upload (nothing is read here); the kernels skip a label >= k."""
+    if not (isinstance(labels_t, torch.Tensor) and labels_t.is_cuda and labels_t.dtype == torch.uint8 and labels_t.dim() == 2
+            and labels_t.is_contiguous() and labels_t.shape[0] >= 1 and labels_t.shape[1] >= 1):
+        raise ValueError(f'{what}: labels_t must be a contiguous (n, R) uint8 device tensor with n >= 1 and R >= 1')
+    if not (isinstance(k, (int, np.integer)) and 2 <= k <= CLUSTER_MAX_CLASSES):
+        raise ValueError(f'{what}: 2 <= k <= {CLUSTER_MAX_CLASSES} classes are needed; got {k!r}')
+    return int(labels_t.shape[0]), int(labels_t.shape[1])
+
+
+def _check_f64(t, shape, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == F64 and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+        raise ValueError(f'{what}: a contiguous float64 device tensor of shape {tuple(shape)} is needed')
+
+
+def _check_gram(G, n, what):
+    _check_matrix(G, what + ' G')
+    if G.dtype != F64 or tuple(G.shape) != (n, n):
+        raise ValueError(f'{what}: G must be the float64 ({n}, {n}) Gram matrix of the labelled rows')
+
+
+def _class_counts(counts, n, R, k, what):
+    """The (R, k) int32 host table of class counts: every count in [0, n], every set adding up to n."""
+    c = np.asarray(counts)
+    if c.shape != (R, k) or c.dtype.kind not in 'iu' or (c < 0).any() or (c.sum(axis=1) != n).any():
+        raise ValueError(f'{what}: counts must be ({R}, {k}) non-negative integers that add up to n = {n} in every label set')
+    return np.ascontiguousarray(c, dtype=np.int32)
+
+
+def label_row_sums(G, labels_t, k, mode):
+    """S (R, n, k) float64: S[r][i][q] = sum over j with labels_t[j][r] == q, j ascending, of G[i][j] (mode 0) or of the euclidean
+    distance sqrt(max(G[i][i] + G[j][j] - 2 G[i][j], 0)), exactly 0 for j == i (mode 1).  G (n, n) float64 device matrix with
+    contiguous rows; labels_t (n, R) uint8 device, values in [0, k).  ONE xps_label_row_sums_f64 launch for all R label sets."""
+    n, R = _check_label_sets(labels_t, k, 'label_row_sums')
+    _check_gram(G, n, 'label_row_sums')
+    if mode not in (0, 1):
+        raise ValueError(f'label_row_sums: mode must be 0 (Gram entries) or 1 (euclidean distances); got {mode!r}')
+    S = torch.empty(R, n, int(k), dtype=F64, device=G.device)
+    call('xps_label_row_sums_f64', G.data_ptr(), G.stride(0), labels_t.data_ptr(), n, R, int(k), int(mode), S.data_ptr(), stream())
+    return S
+
+
+def label_col_sums(V, labels_t, k):
+    """M (R, k, w) float64: M[r][p][c] = sum over i with labels_t[i][r] == p, i ascending, of V[r][i][c].  V: (R, n, w) contiguous
+    float64 device tensor, or (n, w): one table shared by every label set.  ONE xps_label_col_sums_f64 launch."""
+    n, R = _check_label_sets(labels_t, k, 'label_col_sums')
+    if not (isinstance(V, torch.Tensor) and V.dim() in (2, 3) and V.shape[-1] >= 1):
+        raise ValueError('label_col_sums: V must be an (R, n, w) or (n, w) float64 device tensor with w >= 1')
+    w = int(V.shape[-1])
+    _check_f64(V, (R, n, w) if V.dim() == 3 else (n, w), 'label_col_sums V')
+    M = torch.empty(R, int(k), w, dtype=F64, device=V.device)
+    call('xps_label_col_sums_f64', V.data_ptr(), n * w if V.dim() == 3 else 0, labels_t.data_ptr(), n, R, int(k), w, M.data_ptr(),
+         stream())
+    return M
+
+
+def silhouette_from_sums(S, counts, labels_t):
+    """sklearn's silhouette rules on the mode-1 sums S (R, n, k) of label_row_sums: returns (sil, stats, keep) with sil (R, n) the
+    silhouette of every sample under every label set, stats (R, 3) = (mean, mean of the positive values -- NaN when there are
+    none --, number of positive values) and `keep` the host table and workspace of the call, which the caller holds until it has
+    synchronised with the stream.  counts: (R, k) integer HOST array of class counts (an empty class is skipped)."""
+    if not (isinstance(S, torch.Tensor) and S.dim() == 3):
+        raise ValueError('silhouette_from_sums: S must be the (R, n, k) tensor of label_row_sums')
+    k = int(S.shape[2])
+    n, R = _check_label_sets(labels_t, k, 'silhouette_from_sums')
+    _check_f64(S, (R, n, k), 'silhouette_from_sums S')
+    counts = _class_counts(counts, n, R, k, 'silhouette_from_sums')
+    sil = torch.empty(R, n, dtype=F64, device=S.device)
+    stats = torch.empty(R, 3, dtype=F64, device=S.device)
+    nb = int(lib().xps_silhouette_from_sums_f64_workspace(R, k))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=S.device)
+    call('xps_silhouette_from_sums_f64', S.data_ptr(), counts.ctypes.data, labels_t.data_ptr(), n, R, k, sil.data_ptr(),
+         stats.data_ptr(), ws.data_ptr(), nb, stream())
+    return sil, stats, (counts, ws)
+
+
+def centroid_dist_from_sums(G, S0, M, counts, labels_t):
+    """dist (R, n) float64: the distance of every sample to the centroid of its own class under every label set, from the Gram
+    matrix G, the mode-0 sums S0 (R, n, k) and their class-block sums M (R, k, k) = label_col_sums(S0).  Returns (dist, keep);
+    `keep` as in silhouette_from_sums."""
+    if not (isinstance(S0, torch.Tensor) and S0.dim() == 3):
+        raise ValueError('centroid_dist_from_sums: S0 must be the (R, n, k) tensor of label_row_sums')
+    k = int(S0.shape[2])
+    n, R = _check_label_sets(labels_t, k, 'centroid_dist_from_sums')
+    _check_gram(G, n, 'centroid_dist_from_sums')
+    _check_f64(S0, (R, n, k), 'centroid_dist_from_sums S0')
+    _check_f64(M, (R, k, k), 'centroid_dist_from_sums M')
+    counts = _class_counts(counts, n, R, k, 'centroid_dist_from_sums')
+    dist = torch.empty(R, n, dtype=F64, device=S0.device)
+    nb = int(lib().xps_centroid_dist_from_sums_f64_workspace(R, k))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=S0.device)
+    call('xps_centroid_dist_from_sums_f64', G.data_ptr(), G.stride(0), S0.data_ptr(), M.data_ptr(), counts.ctypes.data,
+         labels_t.data_ptr(), n, R, k, dist.data_ptr(), ws.data_ptr(), nb, stream())
+    return dist, (counts, ws)

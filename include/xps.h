@@ -1032,6 +1032,48 @@ int xps_select_channels_f32(const float* x, int N, int T, int C, const int32_t* 
 int xps_select_channels_f64(const double* x, int N, int T, int C, const int32_t* list_start, const int32_t* idx, int S,
                             int Ltot, double* out, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Cluster separability scores (csrc/xps_cluster.hip):            */
+/* label-grouped sums over ONE Gram matrix for R label vectors at once.            */
+/* ------------------------------------------------------------------------- */
+/* The R label vectors of a call are ONE transposed DEVICE array labels_t[j][r] (uint8, n rows of R bytes) with values in
+ * [0, k), 2 <= k <= XPS_CLUSTER_MAX_CLASSES; a label >= k is skipped by every kernel, never used as an index.  All arithmetic
+ * is float64 without atomics, every sum is taken by one lane in ascending index order: the results of a label set do not depend
+ * on the grid, the stream or the other label sets of the call.  Nothing allocates or synchronises; every refusal (null pointers,
+ * n < 1, R < 1, k outside 2..64, ldg < n, ...) is XPS_E_INVALID before any launch.
+ *
+ * xps_label_row_sums_f64: S[r][i][q] = sum over j with y_r[j] = q, j ascending, of f(i, j); S is (R, n, k) contiguous.
+ *   mode 0:  f = G[i][j]
+ *   mode 1:  f = sqrt(max((G[i][i] + G[j][j]) - 2 G[i][j], 0)), each operation rounded once, and exactly 0 for j = i
+ *            (sklearn's euclidean_distances through the Gram matrix; the n x n distance matrix is never stored)
+ * G is n x n with leading dimension ldg >= n.  R <= 64 * 65535.
+ *
+ * xps_label_col_sums_f64: M[r][p][c] = sum over i with y_r[i] = p, i ascending, of V[r][i][c]; V is (R, n, w) with v_set_stride
+ * elements between two sets (>= n * w, or 0: one (n, w) table shared by every set), M is (R, k, w) contiguous, w >= 1.
+ *
+ * xps_silhouette_from_sums_f64: from the mode-1 sums S and the class counts of every set (counts, (R, k) int32, HOST: checked --
+ * each in [0, n], each set adding up to n -- and copied into ws, DEVICE, ..._workspace(R, k) bytes, on the stream; valid until
+ * the stream has passed the call), sklearn.metrics.silhouette_samples: a = own-class sum / (count - 1), b = the smallest
+ * sum / count over the other NON-EMPTY classes, s = (b - a) / max(a, b), 0 for a sample alone in its class and for 0 / 0.
+ * sil is (R, n); stats is (R, 3) = {mean of s, mean of the positive s (NaN when none is), number of positive s}, taken by one
+ * wave per set: lane l adds its terms l, l + 64, ... in ascending order, then the 64 partial sums meet in a fixed butterfly.
+ *
+ * xps_centroid_dist_from_sums_f64: dist[r][i] = sqrt(max(G[i][i] - 2 S0[r][i][p] / n_p + M[r][p][p] / n_p^2, 0)) with p = y_r[i]
+ * and n_p its count: the distance of sample i to the centroid of its own class (Davies-Bouldin), from the mode-0 sums S0
+ * (R, n, k) and their class-block sums M (R, k, k) = xps_label_col_sums_f64 of S0 with w = k.  counts and ws as above. */
+#define XPS_CLUSTER_MAX_CLASSES 64
+int xps_label_row_sums_f64(const double* G, int64_t ldg, const uint8_t* labels_t, int n, int R, int k, int mode, double* S,
+                           void* stream);
+int xps_label_col_sums_f64(const double* V, int64_t v_set_stride, const uint8_t* labels_t, int n, int R, int k, int w, double* M,
+                           void* stream);
+size_t xps_silhouette_from_sums_f64_workspace(int R, int k);
+int xps_silhouette_from_sums_f64(const double* S, const int32_t* counts, const uint8_t* labels_t, int n, int R, int k, double* sil,
+                                 double* stats, void* ws, size_t ws_bytes, void* stream);
+size_t xps_centroid_dist_from_sums_f64_workspace(int R, int k);
+int xps_centroid_dist_from_sums_f64(const double* G, int64_t ldg, const double* S0, const double* M, const int32_t* counts,
+                                    const uint8_t* labels_t, int n, int R, int k, double* dist, void* ws, size_t ws_bytes,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
