@@ -21,6 +21,7 @@ from ..nn_models._lightning import LightningModule
 from .._dev import current_device, stream
 from .._lib import call as _call, rowmap  # noqa: F401
 from .ctc_align import forced_align
+from .ctc_occupancy import posterior_align
 from .ctc_decoder import greedy_decode_batch, greedy_decode_device  # noqa: F401
 
 
@@ -212,18 +213,27 @@ class RealtimeRNNModel(LightningModule):
                                                       total_iters=hp['decay_steps'])
         return [optimizer], [scheduler]
 
-    def forced_align(self, x, targets, target_lengths=None):
-        """x (B, T, C) with its known targets -> CTCAlignment (realtime_sim/ctc_align.py) of the targets through the model's
-        own window log-probabilities: a forward pass in eval mode under no_grad, log-softmax, forced_align.  Frame w of the
-        alignment is window w; window_end_times gives its time."""
+    def _eval_log_probs(self, x):
+        """Window log-probabilities of x (B, T, C): a forward pass in eval mode under no_grad, log-softmax; the mode is put back."""
         was_training = self.training
         self.eval()
         try:
             with torch.no_grad():
-                log_probs = torch.log_softmax(self.forward(x), dim=2)
+                return torch.log_softmax(self.forward(x), dim=2)
         finally:
             self.train(was_training)
-        return forced_align(log_probs, targets, target_lengths=target_lengths, blank=self.blank)
+
+    def forced_align(self, x, targets, target_lengths=None):
+        """x (B, T, C) with its known targets -> CTCAlignment (realtime_sim/ctc_align.py) of the targets through the model's
+        own window log-probabilities: a forward pass in eval mode under no_grad, log-softmax, forced_align.  Frame w of the
+        alignment is window w; window_end_times gives its time."""
+        return forced_align(self._eval_log_probs(x), targets, target_lengths=target_lengths, blank=self.blank)
+
+    def posterior_align(self, x, targets, target_lengths=None):
+        """x (B, T, C) with its known targets -> CTCOccupancy (realtime_sim/ctc_occupancy.py): the forward-backward
+        posteriors of the targets through the model's own window log-probabilities, by forced_align's steps.  Frame w is
+        window w; log_z is -nll."""
+        return posterior_align(self._eval_log_probs(x), targets, target_lengths=target_lengths, blank=self.blank)
 
     def reformat_time_windows(self, x):
         """(B, T, C) -> (B, n_windows, win*C) right-aligned windows (materialised; for inspection only)."""

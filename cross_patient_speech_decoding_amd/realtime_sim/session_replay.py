@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .ctc_align import forced_align
+from .ctc_occupancy import posterior_align
 from .ctc_decoder import _beam_device, check_beam_sizes, greedy_decode_device
 from .realtime_nn_model import per_device
 from .realtime_processing import _check_trials, _good_mask, _hg_trials, _split_coefs, _trial_lengths, _trials_on_device
@@ -36,6 +37,12 @@ class SessionResult:
         over the trial's pred_lengths valid predictions -> CTCAlignment; frame w is prediction w."""
         return forced_align(torch.log_softmax(self.logits, dim=2), targets, input_lengths=self.pred_lengths,
                             target_lengths=target_lengths, blank=self.blank)
+
+    def posterior_align(self, targets, target_lengths=None):
+        """Posterior occupancies (realtime_sim/ctc_occupancy.py) of each trial's known targets through the log-softmax of its
+        logits, over the trial's pred_lengths valid predictions -> CTCOccupancy; frame w is prediction w."""
+        return posterior_align(torch.log_softmax(self.logits, dim=2), targets, input_lengths=self.pred_lengths,
+                               target_lengths=target_lengths, blank=self.blank)
 
     def decoded(self):
         """The tokens as a list of 1-D LongTensors (one transfer of the N lengths)."""

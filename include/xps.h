@@ -471,6 +471,50 @@ int xps_ctc_align(const void* scores, int is_f32, int64_t stride_t, int64_t stri
                   const int64_t* target_lengths, int blank, int32_t* states, int32_t* token_start, int32_t* token_end,
                   double* path_score, void* workspace, size_t workspace_bytes, void* stream);
 
+/* CTC posterior occupancies (realtime_sim/ctc_occupancy.py): the forward-backward posteriors of a KNOWN
+ * target, i.e. how much of the probability mass has token j emitted at, or started at, frame t.  One launch for the batch,
+ * one workgroup per sequence (64 .. 256 lanes, by the states of the longest target), no host synchronisation.
+ * Inputs: exactly xps_ctc_align's, with the same meaning (scores float32 widened exactly, or float64, read in place through
+ *   (stride_t, stride_b) with contiguous classes; lengths clamped to 0..T / 0..Lmax and labels to 0..C-1 for memory safety
+ *   only; padding is never read).  No softmax is applied: a per-frame constant shifts every path alike, so the posteriors
+ *   are the same for logits and their log-softmax and log_z moves by the sum of the constants; with log-probabilities
+ *   log_z = -nll.
+ * Recursion, float64, log domain.  l' = (blank, l_1, blank, ..., l_L, blank), S = 2 L + 1, x_t(c) the widened score,
+ *   [skip s] = s odd, s >= 3 and l'_s != l'_{s-2}; a state index outside 0..S-1 reads as -inf:
+ *     a_0(0) = x_0(blank), a_0(1) = x_0(l_1), else -inf
+ *     a_t(s) = x_t(l'_s) + lse(a_{t-1}(s), a_{t-1}(s-1), [skip s] a_{t-1}(s-2))
+ *     b_{Tb-1}(S-1) = x(l'_{S-1}), b_{Tb-1}(S-2) = x(l'_{S-2}), else -inf
+ *     b_t(s) = x_t(l'_s) + lse(b_{t+1}(s), b_{t+1}(s+1), [skip s+2] b_{t+1}(s+2))
+ *     log_z  = lse(a_{Tb-1}(S-1), a_{Tb-1}(S-2))
+ *     g_t(s) = exp(((a_t(s) + b_t(s)) - x_t(l'_s)) - log_z), 0 where a_t(s) or b_t(s) is -inf
+ *     onset_0(j) = g_0(2j+1)
+ *     onset_t(j) = exp((lse(a_{t-1}(2j), [skip 2j+1] a_{t-1}(2j-1)) + b_t(2j+1)) - log_z), 0 where the lse or b is -inf
+ *   ORDER.  lse(p1, p2, p3) = log((exp(p1 - m) + exp(p2 - m)) + exp(p3 - m)) + m with m = max(p1, max(p2, p3)), the terms in
+ *   the order written above, an absent term -inf (it adds an exact 0), and -inf when m is -inf.  class_occ sums g_t(s) over
+ *   the states of a class by increasing s (the blank column: the even states).  expected_frames and onset_mean add their
+ *   frames from t = Tb - 1 down to 0, onset_mean's term the rounded product (double)t * onset_t(j).  No floating-point
+ *   atomics: two launches give the same bytes, and a sequence's results do not depend on the rest of the batch.
+ * Outputs, float64; log_z is always written, each of the others may be NULL and is then skipped; every element of a
+ *   non-NULL output is written.  log_z [B].  token_occ [B][T][Lmax] = g_t(2j+1).  onset [B][T][Lmax].  class_occ [B][T][C]:
+ *   rows t < Tb sum to 1.  expected_frames [B][Lmax] = sum_t g_t(2j+1).  onset_mean [B][Lmax] = sum_t t onset_t(j).
+ *   Frames t >= Tb and tokens j >= L are 0 in the three tensors; expected_frames is 0 and onset_mean NaN for j >= L.
+ *   log_z = -inf is INFEASIBLE: every posterior 0, expected_frames 0, onset_mean NaN.  Tb = 0: log_z 0 for L = 0, else
+ *   infeasible.  NaN or +inf scores: unspecified values, no out-of-range access.
+ * Workspace: ..._workspace bytes, 8-byte aligned: a_t(s) as one double per (b, t, s) at (b * T + t) * (2 Lmax + 1) + s; only
+ *   t < Tb, s < S are written.
+ * LDS: 80 Lmax + 96 bytes (two rows of a / b with -inf guard cells, g, the two moment rows, the labels and the per-class
+ *   chains), plus 8 C for the class bins when class_occ is given; the kernel's budget is 65536 bytes, so class_occ takes
+ *   C <= 3070 at Lmax = 511 and C <= 8180 at Lmax = 0.
+ * XPS_E_INVALID before any launch: everything xps_ctc_align refuses (a negative size or stride, C < 1, blank outside
+ *   0..C-1, Lmax > 511, target_stride < Lmax, a NULL pointer that the sizes need, a workspace smaller than ..._workspace), an
+ *   output or workspace that is not 8-byte aligned, and class bins that do not fit the LDS budget. */
+size_t xps_ctc_occupancy_workspace(int B, int T, int max_target_len);
+int xps_ctc_occupancy(const void* scores, int is_f32, int64_t stride_t, int64_t stride_b, int T, int B, int C,
+                      int max_target_len, const int64_t* targets, int64_t target_stride, const int64_t* input_lengths,
+                      const int64_t* target_lengths, int blank, double* log_z, double* token_occ, double* onset,
+                      double* class_occ, double* expected_frames, double* onset_mean, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* out[b][:] = table[idx[b]][:]  (embedding / precomputed input projection rows) */
 int xps_gather_rows_f32(const float* table, const int64_t* idx, float* out,
                         int B, int cols, int n_rows, void* stream);
