@@ -1181,3 +1181,83 @@ def centroid_dist_from_sums(G, S0, M, counts, labels_t):
     call('xps_centroid_dist_from_sums_f64', G.data_ptr(), G.stride(0), S0.data_ptr(), M.data_ptr(), counts.ctypes.data,
          labels_t.data_ptr(), n, R, k, dist.data_ptr(), ws.data_ptr(), nb, stream())
     return dist, (counts, ws)
+
+
+# ------------------------------------------------------------------------------------ exact t-SNE (csrc/xps_tsne.hip)
+TSNE_WORDS, TSNE_TILE_ROWS, TSNE_MAX_SAMPLES = 16, 4, 4096   # XPS_TSNE_WORDS, XPS_TSNE_TILE_ROWS, XPS_TSNE_MAX_SAMPLES of include/xps.h
+TSNE_STATE_HEAD, TSNE_STATE_ARRAYS = 8, 15                   # XPS_TSNE_STATE_HEAD, XPS_TSNE_STATE_ARRAYS
+# the words of a problem (include/xps.h)
+(TS_N, TS_NC, TS_G, TS_LDG, TS_D2, TS_C, TS_P, TS_BETA, TS_STEPS, TS_ROWSUM, TS_YIN, TS_YOUT, TS_STATE, TS_ITBEGIN,
+ TS_LR) = range(15)
+
+
+def tsne_tiles(rows):
+    """The int32 tile table of a t-SNE launch (pure numpy): {problem, row tile} for every tile of TSNE_TILE_ROWS rows of every problem, the problems
+    in order and the tiles of a problem ascending.  rows[p]: problem p's row count."""
+    out = [np.stack([np.full(-(-int(n) // TSNE_TILE_ROWS), p), np.arange(-(-int(n) // TSNE_TILE_ROWS))], axis=1)
+           for p, n in enumerate(rows)]
+    return np.ascontiguousarray(np.concatenate(out) if out else np.zeros((0, 2)), dtype=np.int32)
+
+
+def tsne_table(problems):
+    """The int64 problem table of a t-SNE launch from one dict per problem: n, nc and the device tensors / scalars the entry reads
+    (G, D2, C, P, beta, steps, rowsum, Y_in, Y_out, state, it_begin, lr).  Checks every tensor against n before its address is
+    taken; an entry refuses a word it needs and finds 0."""
+    tab = np.zeros((len(problems), TSNE_WORDS), dtype=np.int64)
+    for row, pr in zip(tab, problems):
+        n, nc = int(pr['n']), int(pr.get('nc', 2))
+        if not 2 <= n <= TSNE_MAX_SAMPLES or nc not in (1, 2):
+            raise ValueError(f't-SNE: 2 <= n <= {TSNE_MAX_SAMPLES} samples and 1 or 2 components are needed; got n = {n}, nc = {nc}')
+        row[TS_N], row[TS_NC] = n, nc
+        shapes = dict(D2=((n, n), torch.float32), C=((n, n), F64), P=((n, n), F64), beta=((n,), F64), steps=((n,), torch.int32),
+                      rowsum=((n,), F64), Y_in=((n, nc), F64), Y_out=((n, nc), F64),
+                      state=((2 * (TSNE_STATE_HEAD + TSNE_STATE_ARRAYS * n),), F64))
+        words = dict(D2=TS_D2, C=TS_C, P=TS_P, beta=TS_BETA, steps=TS_STEPS, rowsum=TS_ROWSUM, Y_in=TS_YIN, Y_out=TS_YOUT,
+                     state=TS_STATE)
+        for key, (shape, dtype) in shapes.items():
+            t = pr.get(key)
+            if t is None:
+                continue
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f't-SNE: {key} must be a contiguous {dtype} device tensor of shape {shape}')
+            row[words[key]] = t.data_ptr()
+        if pr.get('G') is not None:
+            _check_gram(pr['G'], n, 't-SNE')
+            row[TS_G], row[TS_LDG] = pr['G'].data_ptr(), pr['G'].stride(0)
+        row[TS_ITBEGIN] = int(pr.get('it_begin', 0))
+        row[TS_LR] = np.float64(pr.get('lr', 0.0)).view(np.int64)
+    return np.ascontiguousarray(tab.reshape(-1))
+
+
+def _tsne_call(name, problems, *args):
+    """One t-SNE entry for a list of problem dicts.  Returns the host tables and the workspace of the call, which the caller keeps
+    until it has synchronised with the stream."""
+    tab = tsne_table(problems)
+    tiles = tsne_tiles([pr['n'] for pr in problems])
+    nb = int(getattr(lib(), name + '_workspace')(len(problems), len(tiles)))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=device())
+    call(name, tab.ctypes.data, len(problems), tiles.ctypes.data, len(tiles), *args, ws.data_ptr(), nb, stream())
+    return tab, tiles, ws
+
+
+def tsne_state(n, dev):
+    """The descent state of a problem of n samples: two halves of 8 + 15 n doubles (include/xps.h)."""
+    return torch.empty(2 * (TSNE_STATE_HEAD + TSNE_STATE_ARRAYS * int(n)), dtype=F64, device=dev)
+
+
+def tsne_sqdist(problems):
+    """D2 = float32(max((G_ii + G_jj) - 2 G_ij, 0)), zero diagonal, for every problem dict (n, G, D2): ONE launch."""
+    return _tsne_call('xps_tsne_sqdist_f32', problems)
+
+
+def tsne_affinities(problems, perplexity):
+    """sklearn's perplexity search and joint probabilities for every problem dict (n, D2, C, P, beta, steps, rowsum): TWO launches."""
+    return _tsne_call('xps_tsne_affinities_f64', problems, float(perplexity))
+
+
+def tsne_descent(problems, n_launches, max_iter, momentum, exaggeration, n_iter_without_progress, min_grad_norm):
+    """One phase of sklearn's _gradient_descent for every problem dict (n, nc, P, Y_in, Y_out, state, it_begin, lr): a priming
+    launch and n_launches iteration launches, enqueued without a host synchronisation.  The result lies in state half
+    n_launches & 1."""
+    return _tsne_call('xps_tsne_descent_f64', problems, int(n_launches), int(max_iter), float(momentum), float(exaggeration),
+                      int(n_iter_without_progress), float(min_grad_norm))

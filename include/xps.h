@@ -1118,6 +1118,81 @@ int xps_centroid_dist_from_sums_f64(const double* G, int64_t ldg, const double* 
                                     const uint8_t* labels_t, int n, int R, int k, double* dist, void* ws, size_t ws_bytes,
                                     void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Exact t-SNE (csrc/xps_tsne.hip; manifold/tsne.py):              */
+/* sklearn's _t_sne.py / _utils.pyx, batched over data sets of different n.        */
+/* ------------------------------------------------------------------------- */
+/* Every entry takes xps_gram_grouped_f64's convention: a HOST table of XPS_TSNE_WORDS int64 words per problem and a HOST tile
+ * table int32[2 * n_tiles] = {problem, row tile}, which must list, for the problems in order, every tile of XPS_TSNE_TILE_ROWS
+ * rows in ascending order (cdiv(n, 4) tiles per problem; one workgroup of four waves each, a wave per row).  The call checks both and copies them into ws
+ * (DEVICE, ..._workspace(n_problems, n_tiles) bytes) on the stream; they stay valid until the stream has passed the call.
+ * Nothing allocates or synchronises.  Refused with XPS_E_INVALID before any launch: null tables, no problem, n outside
+ * 2 .. XPS_TSNE_MAX_SAMPLES, n_components outside {1, 2}, another tile table, a null workspace or one too small, and what each
+ * entry lists.  Words of a problem (an entry reads only those it names):
+ *   0 n   1 n_components   2 G (double, n x n)   3 ldg   4 d2 (float, n x n contiguous)   5 C (double, n x n contiguous)
+ *   6 P (double, n x n contiguous)   7 beta (double, n)   8 steps (int32, n)   9 rowsum (double, n)   10 Y_in (double, n x nc)
+ *   11 Y_out (double, n x nc)   12 state (double, xps_tsne_state_bytes(n) bytes)   13 it_begin   14 learning rate (the bits of a double)
+ *
+ * Float64, no atomics; no operation is contracted into an fma.  SUMMATION ORDER of every sum over j of a row and of every sum
+ * over rows: lane l of one wave adds its terms l, l + 64, ... in ascending order, then the 64 partial sums meet in the fixed
+ * butterfly of xps_silhouette_from_sums_f64.  So a problem's results do not depend on the grid, the batch or the stream.
+ *
+ * xps_tsne_sqdist_f32 (words 0, 2, 3, 4): d2[i][j] = (float)max((G_ii + G_jj) - 2 G_ij, 0), exactly 0 for j = i
+ * (sklearn's euclidean_distances(squared=True) through the Gram matrix, then distances.astype(float32)).  Refused: ldg < n.
+ *
+ * xps_tsne_affinities_f64 (words 0, 4 .. 9), two launches.  The first is _binary_search_perplexity for every row i, one wave
+ * each: beta = 1, beta_min = -inf, beta_max = inf; at most 100 steps of
+ *     sum = sum_{j != i} exp(-d2_ij * beta)   (0 -> (double)1e-8f);      sd = sum_{j != i} d2_ij * (exp(-d2_ij * beta) / sum)
+ *     diff = (log(sum) + beta * sd) - log((double)(float)perplexity);      stop if |diff| <= (double)1e-5f
+ *     diff > 0: beta_min = beta; beta = beta_max == inf ? beta * 2 : (beta + beta_max) / 2
+ *     else:     beta_max = beta; beta = beta_min == -inf ? beta / 2 : (beta + beta_min) / 2
+ * (the .pyx holds the perplexity and both constants in C floats).  C[i][j] = exp(-d2_ij * beta) / sum of the LAST step taken,
+ * C[i][i] = 0; steps[i] = the number of steps taken (100: exhausted); beta[i] = beta as the loop leaves it (after the update of
+ * an exhausted search); rowsum[i] = sum_j C[i][j].  The second launch: S = max(2 sum_i rowsum[i], eps), the sum of all
+ * C_ij + C_ji;  P[i][j] = max((C_ij + C_ji) / S, eps), P[i][i] = 0;  eps = 2.220446049250313e-16.  Refused: a perplexity that
+ * is not positive and finite or not below every n; C == P.
+ *
+ * xps_tsne_descent_f64 (words 0, 1, 6, 10 .. 14): 1 + n_launches launches.  With d = y_i - y_j, q_ij = 1 + |d|^2 (the squares
+ * added component 0 first), w_ij = 1 / q_ij, the PARTIAL SUMS of row i at an embedding are, over j != i,
+ *     s_i = sum w_ij      a_i[c] = sum (P_ij w_ij) d[c]      b_i[c] = sum (w_ij w_ij) d[c]
+ *     e1_i = sum P_ij log(P_ij q_ij)      e2_i = sum P_ij          (e1, e2 only where the next iteration evaluates the error)
+ * Launch 0 PRIMES a phase of _gradient_descent: Y = Y_in, update = 0, gains = 1, error = best error = DBL_MAX, iteration =
+ * best iteration = it_begin, and the partial sums at Y.  Launch t >= 1 runs iteration i of every problem that is not done:
+ *     Z = sum_i s_i;   grad = 4 (e a_i[c] - (1 / Z) b_i[c]),   e = exaggeration
+ *     gains = update * grad < 0 ? gains + 0.2 : gains * 0.8, at least 0.01;   update = momentum * update - lr * (grad * gains)
+ *     Y += update;   at i == max_iter - 1 or (i + 1) % 50 == 0:  error = e ((sum_i e1_i) + log(e Z) (sum_i e2_i)), else NaN
+ *     at (i + 1) % 50 == 0:  error < best error ? best = error, best iteration = i : done if i - best iteration >
+ *         n_iter_without_progress;   done if sqrt(sum_i ((grad gains)[0]^2 + (grad gains)[1]^2)) <= min_grad_norm
+ *     done at i == max_iter - 1;   then the partial sums at the new Y, unless i == max_iter - 1.
+ * This is sklearn's exact _kl_divergence without its clamp Q = max(w / Z, eps): the clamp is inactive while w_ij / Z > eps,
+ * which tests/tsne_ref.py asserts for every case it is held to.  When a problem becomes done its Y (after the step: what
+ * _gradient_descent returns) is written to Y_out; later launches skip it by a uniform branch, so its state stays as it stopped.
+ * STATE: two halves of XPS_TSNE_STATE_HEAD + XPS_TSNE_STATE_ARRAYS * n doubles; launch t reads half (t - 1) & 1 and writes
+ * half t & 1, so the result of the call is in half n_launches & 1.  A half: {iteration (the next to run; sklearn's `it` once
+ * done), error, best error, best iteration, done, Z, gradient norm of the last check, 0}, then the arrays of n doubles
+ * Y[0] Y[1] update[0] update[1] gains[0] gains[1] grad[0] grad[1] s a[0] a[1] b[0] b[1] e1 e2 (component 1 of a
+ * one-component problem: Y = update = grad = 0, gains = 1).  The problem's first workgroup alone writes the first eight
+ * arrays and the head; every workgroup rebuilds the step in LDS from the read half and writes the partial sums of its rows.
+ * Y_in may be Y_out.  Refused: n_launches < 0, max_iter < 1, it_begin outside 0 .. max_iter - 1, a momentum that is negative or
+ * not finite, an exaggeration or a learning rate that is not positive and finite, n_iter_without_progress < 0, a NaN
+ * min_grad_norm, null P / Y_in / Y_out / state. */
+#define XPS_TSNE_WORDS 16
+#define XPS_TSNE_TILE_ROWS 4
+#define XPS_TSNE_MAX_SAMPLES 4096
+#define XPS_TSNE_STATE_HEAD 8
+#define XPS_TSNE_STATE_ARRAYS 15
+size_t xps_tsne_state_bytes(int n);
+size_t xps_tsne_sqdist_f32_workspace(int n_problems, int n_tiles);
+int xps_tsne_sqdist_f32(const int64_t* problems, int n_problems, const int32_t* tiles, int n_tiles, void* ws, size_t ws_bytes,
+                        void* stream);
+size_t xps_tsne_affinities_f64_workspace(int n_problems, int n_tiles);
+int xps_tsne_affinities_f64(const int64_t* problems, int n_problems, const int32_t* tiles, int n_tiles, double perplexity, void* ws,
+                            size_t ws_bytes, void* stream);
+size_t xps_tsne_descent_f64_workspace(int n_problems, int n_tiles);
+int xps_tsne_descent_f64(const int64_t* problems, int n_problems, const int32_t* tiles, int n_tiles, int n_launches, int max_iter,
+                         double momentum, double exaggeration, int n_iter_without_progress, double min_grad_norm, void* ws,
+                         size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
