@@ -1,6 +1,7 @@
 from . import augmentations  # noqa: F401
 from .ctc_align import CTCAlignment, forced_align, window_end_times  # noqa: F401
 from .ctc_occupancy import CTCOccupancy, posterior_align  # noqa: F401
+from .ctc_errors import EditAlignment, edit_align  # noqa: F401
 from .ctc_decoder import beam_decode_batch, beam_decode_torch, decode, greedy_decode_batch, greedy_decode_device  # noqa: F401
 from .realtime_datamodule import (CTCDataset, CTCHeldOutDataModule, CTCHeldOutTargetValAlignCVDataModule,  # noqa: F401
                                   CTCHeldOutTargetValAlignDataModule, CTCHeldOutTargetValCVDataModule,

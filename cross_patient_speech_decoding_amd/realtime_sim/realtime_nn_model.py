@@ -23,6 +23,7 @@ from .._lib import call as _call, rowmap  # noqa: F401
 from .ctc_align import forced_align
 from .ctc_occupancy import posterior_align
 from .ctc_decoder import greedy_decode_batch, greedy_decode_device  # noqa: F401
+from .ctc_errors import edit_align
 
 
 class StackedRNN(nn.Module):
@@ -234,6 +235,22 @@ class RealtimeRNNModel(LightningModule):
         posteriors of the targets through the model's own window log-probabilities, by forced_align's steps.  Frame w is
         window w; log_z is -nll."""
         return posterior_align(self._eval_log_probs(x), targets, target_lengths=target_lengths, blank=self.blank)
+
+    def decode_errors(self, x, targets, target_lengths=None, input_lengths=None):
+        """x (B, T, C) with its known targets -> EditAlignment (realtime_sim/ctc_errors.py) of the model's own greedy decode
+        against them: a forward pass in eval mode under no_grad, greedy_decode_device, edit_align with the model's classes,
+        so .confusion is the (n_classes + 1, n_classes + 1) phoneme confusion matrix of the batch.  target_lengths None: all
+        of targets' columns.  input_lengths (B,), the valid input rows of each trial (None: all T): the windows past a
+        trial's adjusted length, (input_length - win_size) // stride + 1, are decoded as blank."""
+        lp = self._eval_log_probs(x)
+        if input_lengths is not None:
+            il = torch.as_tensor(input_lengths).to(lp.device).reshape(-1, 1)
+            past = torch.arange(lp.size(1), device=lp.device)[None, :] >= self._adjusted_lengths(il)
+            pad = torch.full((lp.size(2),), -float('inf'), dtype=lp.dtype, device=lp.device)
+            pad[self.blank] = 0.0
+            lp = torch.where(past[:, :, None], pad, lp)
+        tokens, lengths = greedy_decode_device(lp, blank=self.blank)
+        return edit_align(tokens, lengths, targets, target_lengths, n_classes=self.classifier.fc.out_features)
 
     def reformat_time_windows(self, x):
         """(B, T, C) -> (B, n_windows, win*C) right-aligned windows (materialised; for inspection only)."""

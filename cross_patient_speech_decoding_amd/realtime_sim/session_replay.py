@@ -15,6 +15,7 @@ import torch
 from .ctc_align import forced_align
 from .ctc_occupancy import posterior_align
 from .ctc_decoder import _beam_device, check_beam_sizes, greedy_decode_device
+from .ctc_errors import edit_align
 from .realtime_nn_model import per_device
 from .realtime_processing import _check_trials, _good_mask, _hg_trials, _split_coefs, _trial_lengths, _trials_on_device
 
@@ -43,6 +44,13 @@ class SessionResult:
         logits, over the trial's pred_lengths valid predictions -> CTCOccupancy; frame w is prediction w."""
         return posterior_align(torch.log_softmax(self.logits, dim=2), targets, input_lengths=self.pred_lengths,
                                target_lengths=target_lengths, blank=self.blank)
+
+    def errors(self, targets, target_lengths=None, n_classes=None):
+        """Edit-operation alignment (realtime_sim/ctc_errors.py) of each trial's decoded tokens against its known targets ->
+        EditAlignment: the hits, substitutions, deletions and insertions behind `per`, the maps between the two sequences
+        and, with n_classes, the phoneme confusion matrix.  The tokens are -1 padded; token_lengths govern.
+        target_lengths None: all of targets' columns."""
+        return edit_align(self.tokens, self.token_lengths, targets, target_lengths, n_classes=n_classes)
 
     def decoded(self):
         """The tokens as a list of 1-D LongTensors (one transfer of the N lengths)."""

@@ -1038,6 +1038,48 @@ int xps_edit_distance_supported(int max_pred_len, int max_tgt_len);
 int xps_edit_distance_i64(const int64_t* pred, int64_t pred_stride, const int64_t* pred_len, const int64_t* tgt,
                           int64_t tgt_stride, const int64_t* tgt_len, int B, int max_pred_len, int max_tgt_len,
                           int64_t* dist, void* stream);
+/* Edit-operation alignment (csrc/xps_edit_align.hip, realtime_sim/ctc_errors.py): the Levenshtein
+ * alignment behind the distance, i.e. WHICH tokens were hit, substituted, deleted and inserted.  One launch for the batch, one
+ * wave per pair, no host synchronisation, no allocation; a pair's per-pair outputs do not depend on the rest of its batch.
+ * Inputs: exactly xps_edit_distance_i64's, with the same meaning (pred [B][pred_stride] int64 with pred_len [B], tgt
+ *   [B][tgt_stride] int64 with tgt_len [B]; max_pred_len <= 65536, max_tgt_len <= 1024; a length entry is clamped to
+ *   0..max_pred_len / 0..max_tgt_len; padding is never read), and n_classes = K, read only when `confusion` is given.
+ * Names.  A HIT is a prediction token aligned to an equal target token, a SUBSTITUTION one aligned to an unequal target
+ *   token, an INSERTION a prediction token aligned to nothing, a DELETION a target token aligned to nothing.
+ * Table, a = pred of length m, t = tgt of length n, tokens 1-based:
+ *     D[i][0] = i,  D[0][j] = j,
+ *     D[i][j] = min(D[i-1][j-1] + [a_i != t_j], D[i-1][j] + 1, D[i][j-1] + 1).
+ * TIE RULE (part of the contract, stated on D alone so that no evaluation order can change it).  Walk back from (m, n).  At
+ *   a cell with i > 0 and j > 0: take the diagonal (i-1, j-1) if D[i][j] == D[i-1][j-1] + [a_i != t_j]; else the insertion
+ *   (i-1, j) if D[i][j] == D[i-1][j] + 1; else the deletion (i, j-1).  On the border i = 0 there are only deletions, on the
+ *   border j = 0 only insertions.  A diagonal step aligns a_i with t_j (a hit when they are equal, else a substitution).
+ * Outputs; `dist` is always written, each of the others may be NULL and is then skipped; every element of a non-NULL
+ *   per-pair output is written.
+ *   dist [B] int64 = D[m][n] (= xps_edit_distance_i64's).
+ *   counts [B][4] int64 = hits, substitutions, deletions, insertions: hits + substitutions + deletions = n,
+ *     hits + substitutions + insertions = m, substitutions + deletions + insertions = dist.
+ *   tgt_to_pred [B][max_tgt_len] int32: the 0-based index of the prediction token aligned to target token j, -1 for a
+ *     deleted one, -2 for j >= n.
+ *   pred_to_tgt [B][max_pred_len] int32: the 0-based index of the target token aligned to prediction token i, -1 for an
+ *     inserted one, -2 for i >= m.
+ *   confusion [K+1][K+1] int64, ADDED INTO (the caller zeroes it; launches and batches accumulate into one matrix): row =
+ *     target class, row K = no target (an insertion); column = predicted class, column K = nothing (a deletion); one count
+ *     per step of the walk, so cell (K, K) is never touched.  64-bit integer atomic adds, no floating point: the sum does
+ *     not depend on the order and two runs give the same bytes.  (K + 1)^2 <= 8192 cells are first summed per workgroup
+ *     (4 pairs) in LDS and reach the matrix as one add per non-zero cell; a larger matrix takes one add per step of the
+ *     walk; no result depends on that route.  Labels outside 0..K-1 are the caller's to refuse; the
+ *     kernel clamps them to 0..K-1 for the cell index only (memory safety), never for the comparison a_i != t_j.
+ * Workspace: ..._workspace bytes, one backpointer byte per cell at (b * max_pred_len + i - 1) * max_tgt_len + j - 1
+ *   (0 hit, 1 substitution, 2 insertion, 3 deletion: the tie rule evaluated in the forward pass); only cells with
+ *   1 <= i <= m and 1 <= j <= n may be written.
+ * XPS_E_INVALID before any launch: everything xps_edit_distance_i64 refuses (B < 0, lengths outside
+ *   xps_edit_distance_supported, a stride shorter than its padded length), K < 1 when `confusion` is given, a NULL pointer
+ *   that the sizes need, a workspace that is NULL or smaller than ..._workspace. */
+size_t xps_edit_align_workspace(int B, int max_pred_len, int max_tgt_len);
+int xps_edit_align(const int64_t* pred, int64_t pred_stride, const int64_t* pred_len, const int64_t* tgt,
+                   int64_t tgt_stride, const int64_t* tgt_len, int B, int max_pred_len, int max_tgt_len, int n_classes,
+                   int64_t* dist, int64_t* counts, int32_t* tgt_to_pred, int32_t* pred_to_tgt, int64_t* confusion,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Electrode subsampling (csrc/xps_subsample.hip): spatial        */
