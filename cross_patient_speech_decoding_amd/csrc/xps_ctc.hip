@@ -11,10 +11,11 @@
 // alpha_t(s) = lp_t(l'_s) + logsumexp(alpha_{t-1}(s), alpha_{t-1}(s-1), [l'_s != l'_{s-2}] alpha_{t-1}(s-2)),
 // nll = -logsumexp(alpha_{T-1}(S-1), alpha_{T-1}(S-2)); d nll / d logit_t(c) = exp(lp_t(c)) - exp(logsumexp_{s: l'_s = c}
 // (alpha_t(s) + beta_t(s)) + nll - lp_t(c)); zero beyond the input length; reduction 'mean' = mean_b(nll_b / max(L_b, 1)).
-#include "xps_common.h"
+// The state cap CTC_MAXS is xps_ctc_lattice.h's, one number for this kernel, the best path and the occupancies; nothing
+// else of that header is used here (the skip rule below is written on labels, lse3 is the float one).
+#include "xps_ctc_lattice.h"          // CTC_MAXS: 2 * max target length + 1 states held in LDS
 
 namespace {
-constexpr int CTC_MAXS = 1024;       // 2 * max target length + 1 states held in LDS
 constexpr float NEG_INF = -INFINITY;
 
 __device__ inline float lse3(float a, float b, float c) {

@@ -1,6 +1,8 @@
 // CTC forced alignment: the Viterbi best path of a KNOWN target sequence through per-frame scores (the max-plus twin of
 // the alpha recursion in xps_ctc.hip), its per-frame states, per-token frame spans and score.  One 64-lane workgroup per
-// sequence, one launch for the batch, no host synchronisation, no allocation.
+// sequence, one launch for the batch, no host synchronisation, no allocation.  The lattice set-up (state cap, clamped
+// extents, extended labels, skip rule, the entry's common checks and launch pair) is xps_ctc_lattice.h's, shared with
+// xps_ctc_occupancy.hip.
 //
 // Contract (include/xps.h has the same text).  Extended label l' = (blank, l_1, blank, ..., l_L, blank), S = 2 L + 1 states,
 // x_t(c) the score of class c at frame t widened to float64; everything below is float64 additions and comparisons:
@@ -15,11 +17,9 @@
 // one-byte loads by one lane.  The two rows of v and the labels live in LDS sized by the batch's longest target (lanes
 // stride over s); the backpointers, one byte per (t, s), go to the caller's workspace at ((b * T + t) * Smax + s),
 // Smax = 2 * max_target_len + 1: only t in 1..Tb-1 and s < S of a sequence are written.
-#include "xps_common.h"
+#include "xps_ctc_lattice.h"
 
 namespace {
-constexpr int ALIGN_MAXS = 1024;     // the loss kernel's state cap (CTC_MAXS in xps_ctc.hip)
-
 // two rows of Smax + 2 doubles and Smax labels, Smax = 2 * Lmax + 1: 20.5 KB at the cap, 232 bytes at Lmax = 5
 inline size_t align_lds_bytes(int Lmax) {
     const size_t Smax = 2 * (size_t)Lmax + 1;
@@ -37,11 +37,8 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const T* __restrict__ sco
     extern __shared__ double lds[];             // align_lds_bytes(Lmax): sized by the batch's longest target, not by the cap
     const int b = blockIdx.x, lane = threadIdx.x;
     const double NINF = -INFINITY;
-    long long tb = in_len ? in_len[b] : (long long)Tn;
-    const int Tb = tb < 0 ? 0 : (tb > Tn ? Tn : (int)tb);
-    long long lb = tg_len ? tg_len[b] : (long long)Lmax;
-    const int Lb = lb < 0 ? 0 : (lb > Lmax ? Lmax : (int)lb);
-    const int S = 2 * Lb + 1, Smax = 2 * Lmax + 1;
+    const CtcExtent e = ctc_extent(in_len, tg_len, b, Tn, Lmax);
+    const int Tb = e.Tb, Lb = e.Lb, S = e.S, Smax = e.Smax;
     double* const row0 = lds;                   // the two rows of v, index s + 2: two -inf guards in front
     double* const row1 = lds + Smax + 2;
     int* const lab = reinterpret_cast<int*>(lds + 2 * (Smax + 2));
@@ -52,10 +49,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const T* __restrict__ sco
     int* ts = tok_start + (long long)b * Lmax;
     int* te = tok_end + (long long)b * Lmax;
 
-    for (int s = lane; s < S; s += 64) {
-        long long l = (s & 1) ? tgt[s >> 1] : (long long)blank;
-        lab[s] = l < 0 ? 0 : (l >= C ? C - 1 : (int)l);         // memory safety only: labels are the caller's contract
-    }
+    ctc_fill_labels(lab, tgt, S, blank, C, lane, 64);
     for (int s = lane; s < S + 2; s += 64) { row0[s] = NINF; row1[s] = NINF; }
     for (int t = Tb + lane; t < Tn; t += 64) st[t] = -1;
     for (int j = lane; j < Lmax; j += 64) { ts[j] = -1; te[j] = -1; }
@@ -78,7 +72,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const T* __restrict__ sco
             int k = 0;
             const double a1 = prev[s + 1];                      // s == 0: the -inf guard, never strictly larger
             if (a1 > m) { m = a1; k = 1; }
-            if ((s & 1) && s >= 3 && lab[s] != lab[s - 2]) {
+            if (ctc_skip(lab, s)) {
                 const double a2 = prev[s];
                 if (a2 > m) { m = a2; k = 2; }
             }
@@ -121,29 +115,15 @@ extern "C" int xps_ctc_align(const void* scores, int is_f32, int64_t stride_t, i
                              const int64_t* input_lengths, const int64_t* target_lengths, int blank, int32_t* states,
                              int32_t* token_start, int32_t* token_end, double* path_score, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    XPS_CHECK_ARG(T >= 0 && B >= 0 && max_target_len >= 0 && stride_t >= 0 && stride_b >= 0, "negative size");
-    XPS_CHECK_ARG(C >= 1, "needs at least one class");
-    XPS_CHECK_ARG(blank >= 0 && blank < C, "blank outside 0..C-1");
-    XPS_CHECK_ARG(2 * (long long)max_target_len + 1 <= ALIGN_MAXS, "target longer than 511 labels");
-    XPS_CHECK_ARG(target_stride >= max_target_len, "target stride smaller than the longest target");
+    XPS_CTC_CHECK_LATTICE_ARGS();
     if (B == 0) return XPS_OK;
     XPS_CHECK_ARG(path_score, "null argument");
     XPS_CHECK_ARG((scores && states) || T == 0, "null argument");
     XPS_CHECK_ARG((targets && token_start && token_end) || max_target_len == 0, "null argument");
     XPS_CHECK_ARG(workspace && workspace_bytes >= xps_ctc_align_workspace(B, T, max_target_len), "workspace too small");
-    const long long* tg = reinterpret_cast<const long long*>(targets);
-    const long long* il = reinterpret_cast<const long long*>(input_lengths);
-    const long long* tl = reinterpret_cast<const long long*>(target_lengths);
     unsigned char* bp = reinterpret_cast<unsigned char*>(workspace);
-    const size_t lds = align_lds_bytes(max_target_len);
-    if (is_f32)
-        hipLaunchKernelGGL(ctc_align_kernel<float>, dim3(B), dim3(64), lds, (hipStream_t)stream, (const float*)scores,
-                           (long long)stride_t, (long long)stride_b, T, C, max_target_len, tg, (long long)target_stride, il, tl,
-                           blank, states, token_start, token_end, path_score, bp);
-    else
-        hipLaunchKernelGGL(ctc_align_kernel<double>, dim3(B), dim3(64), lds, (hipStream_t)stream, (const double*)scores,
-                           (long long)stride_t, (long long)stride_b, T, C, max_target_len, tg, (long long)target_stride, il, tl,
-                           blank, states, token_start, token_end, path_score, bp);
+    XPS_CTC_LAUNCH(ctc_align_kernel, dim3(B), dim3(64), align_lds_bytes(max_target_len), states, token_start, token_end,
+                   path_score, bp);
     XPS_CHECK_LAUNCH();
     return XPS_OK;
 }

@@ -9,9 +9,8 @@
 //     warp    ATen upsample_linear1d (align_corners = False) T -> T2[n] -> T, fp32, fused: the intermediate row is never stored
 //   greedy CTC decode        argmax per frame (first maximum, NaN = maximum like torch.argmax) -> collapse repeats -> drop
 //                            blanks; one wave per sequence, frames across the lanes, compaction by ballot; one launch per batch
-//   edit distance            unit-cost Levenshtein, one wave per (prediction, target) pair, target columns across the lanes in
-//                            chunks of 64 held in registers; the in-row dependency cur[j] = min(tmp[j], cur[j-1] + 1) is the
-//                            prefix minimum cur[j] = j + min_{k <= j}(tmp[k] - k), a 6-step wave scan
+// The edit distance of the decoded batch (xps_edit_distance_i64) is the row pass of the edit-operation alignment and lives
+// with it in xps_edit_align.hip.
 #include "xps_common.h"
 
 namespace {
@@ -170,82 +169,6 @@ __global__ __launch_bounds__(256) void greedy_decode_kernel(const TI* __restrict
     if (lane == 0) lengths[b] = count;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// batched unit-cost Levenshtein distance: one wave per pair, NCH register chunks of 64 target columns
-constexpr int ED_BIG = 1 << 29;
-
-__device__ inline int wave_prefix_min(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d, 64);
-        if (lane >= d) v = o < v ? o : v;
-    }
-    return v;
-}
-
-template <int NCH>
-__global__ __launch_bounds__(256) void edit_distance_kernel(const long long* __restrict__ pred, long long pred_stride,
-                                                            const long long* __restrict__ pred_len, const long long* __restrict__ tgt,
-                                                            long long tgt_stride, const long long* __restrict__ tgt_len, int B,
-                                                            int max_pred, int max_tgt, long long* __restrict__ dist) {
-    const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= B) return;
-    long long ml = pred_len[b], nl = tgt_len[b];
-    const int m = ml < 0 ? 0 : (ml > max_pred ? max_pred : (int)ml);    // lengths clamped to the padded extents: no read outside
-    const int n = nl < 0 ? 0 : (nl > max_tgt ? max_tgt : (int)nl);
-    const long long* a = pred + (long long)b * pred_stride;
-    const long long* t = tgt + (long long)b * tgt_stride;
-    int prev[NCH];                 // prev[c] = D[i-1][j], j = 64 c + lane + 1
-    long long tg[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int j = 64 * c + lane + 1;
-        prev[c] = j;
-        tg[c] = j <= n ? t[j - 1] : 0;
-    }
-    const int nch = (n + 63) >> 6;                                       // chunks in use (wave-uniform)
-    for (int i0 = 0; i0 < m; i0 += 64) {
-        const long long mine = i0 + lane < m ? a[i0 + lane] : 0;         // 64 prediction tokens per load, broadcast per row
-        const int rows = m - i0 < 64 ? m - i0 : 64;
-        for (int r = 0; r < rows; ++r) {
-            const long long tok = __shfl(mine, r, 64);
-            const int i = i0 + r + 1;
-            int diag = i - 1;                                            // D[i-1][64 c]   (column before the chunk)
-            int left = i;                                                // D[i][64 c]
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                if (c < nch) {
-                    const int j = 64 * c + lane + 1;
-                    const int up = prev[c];
-                    int ul = __shfl_up(up, 1, 64);
-                    if (lane == 0) ul = diag;
-                    const int sub = ul + (tok != tg[c] ? 1 : 0);
-                    int tmp = up + 1 < sub ? up + 1 : sub;
-                    const int v = wave_prefix_min(j <= n ? tmp - j : ED_BIG, lane);
-                    const int lft = left - 64 * c;                       // (D[i][64 c] + 1) - (64 c + 1): the carried-in run
-                    const int cur = j + (v < lft ? v : lft);
-                    diag = __shfl(up, 63, 64);
-                    left = __shfl(cur, 63, 64);
-                    prev[c] = j <= n ? cur : j;
-                }
-            }
-        }
-    }
-    int res = m;                                                         // n == 0: D[m][0]
-    if (n > 0) {
-        const int c_last = (n - 1) >> 6, l_last = (n - 1) & 63;
-        int val = 0;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-            if (c == c_last) val = prev[c];
-        res = __shfl(val, l_last, 64);
-    }
-    if (lane == 0) dist[b] = res;
-}
-
-constexpr int ED_MAX_PRED = 65536, ED_MAX_TGT = 1024;
-
 }  // namespace
 
 extern "C" int xps_aug_trial_shift_f32(const float* x, float* out, int N, int T, int C, const int64_t* shift, void* stream) {
@@ -316,36 +239,6 @@ extern "C" int xps_ctc_greedy_decode(const void* logits, int is_f32, int64_t str
     else
         hipLaunchKernelGGL(greedy_decode_kernel<double>, dim3(cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, (const double*)logits,
                            (long long)stride_t, (long long)stride_b, T, B, C, blank, tk, ln);
-    XPS_CHECK_LAUNCH();
-    return XPS_OK;
-}
-
-extern "C" int xps_edit_distance_supported(int max_pred_len, int max_tgt_len) {
-    return max_pred_len >= 0 && max_pred_len <= ED_MAX_PRED && max_tgt_len >= 0 && max_tgt_len <= ED_MAX_TGT;
-}
-
-extern "C" int xps_edit_distance_i64(const int64_t* pred, int64_t pred_stride, const int64_t* pred_len, const int64_t* tgt,
-                                     int64_t tgt_stride, const int64_t* tgt_len, int B, int max_pred_len, int max_tgt_len,
-                                     int64_t* dist, void* stream) {
-    XPS_CHECK_ARG(B >= 0, "bad argument");
-    XPS_CHECK_ARG(xps_edit_distance_supported(max_pred_len, max_tgt_len), "sequence lengths outside the supported range");
-    XPS_CHECK_ARG(pred_stride >= max_pred_len && tgt_stride >= max_tgt_len, "row stride shorter than the padded length");
-    if (B == 0) return XPS_OK;
-    XPS_CHECK_ARG(pred_len && tgt_len && dist, "null argument");
-    XPS_CHECK_ARG((pred || max_pred_len == 0) && (tgt || max_tgt_len == 0), "null argument");
-    const long long* p = reinterpret_cast<const long long*>(pred);
-    const long long* pl = reinterpret_cast<const long long*>(pred_len);
-    const long long* t = reinterpret_cast<const long long*>(tgt);
-    const long long* tl = reinterpret_cast<const long long*>(tgt_len);
-    long long* d = reinterpret_cast<long long*>(dist);
-    const dim3 grid(cdiv(B, 4)), block(256);
-#define XPS_ED_LAUNCH(NCH)                                                                                                      \
-    hipLaunchKernelGGL(edit_distance_kernel<NCH>, grid, block, 0, (hipStream_t)stream, p, (long long)pred_stride, pl, t,          \
-                       (long long)tgt_stride, tl, B, max_pred_len, max_tgt_len, d)
-    if (max_tgt_len <= 64) XPS_ED_LAUNCH(1);
-    else if (max_tgt_len <= 256) XPS_ED_LAUNCH(4);
-    else XPS_ED_LAUNCH(16);
-#undef XPS_ED_LAUNCH
     XPS_CHECK_LAUNCH();
     return XPS_OK;
 }

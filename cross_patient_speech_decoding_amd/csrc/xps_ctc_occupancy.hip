@@ -2,7 +2,9 @@
 // of the probability mass has token j emitted at frame t (token_occ), started at frame t (onset), and class c emitted at
 // frame t (class_occ) -- with log Z and the two first moments (expected_frames, onset_mean).  The sum-product twin of the
 // best path in xps_ctc_align.hip.  One workgroup per sequence, one launch for the batch, no host synchronisation, no
-// allocation, no floating-point atomics.
+// allocation, no floating-point atomics.  The lattice set-up (state cap, clamped extents, extended labels, skip rule, the
+// entry's common checks and launch pair) is xps_ctc_lattice.h's, shared with xps_ctc_align.hip; the double lse3 stays here:
+// its term order is contract.
 //
 // Contract: include/xps.h (the recursion, the order of the terms of every lse and of every sum, the edge rules).
 //
@@ -17,12 +19,11 @@
 // Class sums: the states of one class form a chain by increasing s (built once per sequence); the lane of the chain's first
 // state adds g along it into the class's LDS bin, then the lanes copy the C bins out.  One barrier per frame, two with
 // class_occ.
-#include "xps_common.h"
+#include "xps_ctc_lattice.h"
 
 #include <cstdint>
 
 namespace {
-constexpr int OCC_MAXS = 1024;          // the loss kernel's state cap (CTC_MAXS in xps_ctc.hip): 2 * 511 + 1 states
 constexpr int OCC_MAX_WIDTH = 256;
 constexpr size_t OCC_LDS_BUDGET = 65536;
 constexpr int OCC_HEAD = 0x10000, OCC_END = 0xFFFF;
@@ -60,11 +61,8 @@ __global__ __launch_bounds__(OCC_MAX_WIDTH) void ctc_occupancy_kernel(
     extern __shared__ __attribute__((aligned(16))) double lds[];    // occ_lds_bytes(Lmax, C, class_occ != NULL)
     const int b = blockIdx.x, tid = threadIdx.x, W = blockDim.x;
     const double NINF = -INFINITY;
-    long long tb = in_len ? in_len[b] : (long long)Tn;
-    const int Tb = tb < 0 ? 0 : (tb > Tn ? Tn : (int)tb);
-    long long lb = tg_len ? tg_len[b] : (long long)Lmax;
-    const int Lb = lb < 0 ? 0 : (lb > Lmax ? Lmax : (int)lb);
-    const int S = 2 * Lb + 1, Smax = 2 * Lmax + 1;
+    const CtcExtent e = ctc_extent(in_len, tg_len, b, Tn, Lmax);
+    const int Tb = e.Tb, Lb = e.Lb, S = e.S, Smax = e.Smax;
     double* const row0 = lds;                       // index s + 2: two -inf guards in front, two behind state S - 1
     double* const row1 = row0 + Smax + 4;
     double* const g = row1 + Smax + 4;
@@ -80,10 +78,7 @@ __global__ __launch_bounds__(OCC_MAX_WIDTH) void ctc_occupancy_kernel(
     double* const ons = onset ? onset + (long long)b * Tn * Lmax : nullptr;
     double* const cls = class_occ ? class_occ + (long long)b * Tn * C : nullptr;
 
-    for (int s = tid; s < S; s += W) {
-        long long l = (s & 1) ? tgt[s >> 1] : (long long)blank;
-        lab[s] = l < 0 ? 0 : (l >= C ? C - 1 : (int)l);             // memory safety only: labels are the caller's contract
-    }
+    ctc_fill_labels(lab, tgt, S, blank, C, tid, W);
     for (int s = tid; s < Smax + 4; s += W) { row0[s] = NINF; row1[s] = NINF; }
     for (int j = tid; j < Lmax; j += W) { ef[j] = 0.0; om[j] = 0.0; }
     if (cls)
@@ -123,7 +118,7 @@ __global__ __launch_bounds__(OCC_MAX_WIDTH) void ctc_occupancy_kernel(
             double* at = aw + (long long)t * Smax;
             for (int s = tid; s < S; s += W) {
                 const double xs = (double)p[lab[s]];
-                const bool skip = (s & 1) && s >= 3 && lab[s] != lab[s - 2];
+                const bool skip = ctc_skip(lab, s);
                 const double a = xs + lse3(prev[s + 2], prev[s + 1], skip ? prev[s] : NINF);
                 cur[s + 2] = a;
                 at[s] = a;
@@ -168,7 +163,7 @@ __global__ __launch_bounds__(OCC_MAX_WIDTH) void ctc_occupancy_kernel(
             }
             const double a = at[s];
             const bool odd = s & 1;
-            const bool skip_in = odd && s >= 3 && lab[s] != lab[s - 2];
+            const bool skip_in = ctc_skip(lab, s);
             double p1 = NINF, p2 = NINF;
             if (odd && t > 0) {
                 p1 = at[s - 1 - Smax];                               // a_{t-1}(2j)
@@ -179,7 +174,7 @@ __global__ __launch_bounds__(OCC_MAX_WIDTH) void ctc_occupancy_kernel(
             if (t == Tb - 1)
                 bt = s >= S - 2 ? xs : NINF;
             else {
-                const bool skip_out = odd && s + 2 < S && lab[s + 2] != lab[s];
+                const bool skip_out = s + 2 < S && ctc_skip(lab, s + 2);
                 bt = xs + lse3(nxt[s + 2], nxt[s + 3], skip_out ? nxt[s + 4] : NINF);
             }
             cur[s + 2] = bt;
@@ -232,11 +227,7 @@ extern "C" int xps_ctc_occupancy(const void* scores, int is_f32, int64_t stride_
                                  const int64_t* input_lengths, const int64_t* target_lengths, int blank, double* log_z,
                                  double* token_occ, double* onset, double* class_occ, double* expected_frames,
                                  double* onset_mean, void* workspace, size_t workspace_bytes, void* stream) {
-    XPS_CHECK_ARG(T >= 0 && B >= 0 && max_target_len >= 0 && stride_t >= 0 && stride_b >= 0, "negative size");
-    XPS_CHECK_ARG(C >= 1, "needs at least one class");
-    XPS_CHECK_ARG(blank >= 0 && blank < C, "blank outside 0..C-1");
-    XPS_CHECK_ARG(2 * (long long)max_target_len + 1 <= OCC_MAXS, "target longer than 511 labels");
-    XPS_CHECK_ARG(target_stride >= max_target_len, "target stride smaller than the longest target");
+    XPS_CTC_CHECK_LATTICE_ARGS();
     if (B == 0) return XPS_OK;
     XPS_CHECK_ARG(log_z, "null argument");
     XPS_CHECK_ARG(scores || T == 0, "null argument");
@@ -247,21 +238,9 @@ extern "C" int xps_ctc_occupancy(const void* scores, int is_f32, int64_t stride_
                   "output or workspace not 8-byte aligned");
     const size_t lds = occ_lds_bytes(max_target_len, C, class_occ != nullptr);
     XPS_CHECK_ARG(lds <= OCC_LDS_BUDGET, "class bins exceed the LDS budget");
-    const long long* tg = reinterpret_cast<const long long*>(targets);
-    const long long* il = reinterpret_cast<const long long*>(input_lengths);
-    const long long* tl = reinterpret_cast<const long long*>(target_lengths);
     double* aw = reinterpret_cast<double*>(workspace);
-    const int width = occ_width(max_target_len);
-    if (is_f32)
-        hipLaunchKernelGGL(ctc_occupancy_kernel<float>, dim3(B), dim3(width), lds, (hipStream_t)stream,
-                           (const float*)scores, (long long)stride_t, (long long)stride_b, T, C, max_target_len, tg,
-                           (long long)target_stride, il, tl, blank, log_z, token_occ, onset, class_occ, expected_frames,
-                           onset_mean, aw);
-    else
-        hipLaunchKernelGGL(ctc_occupancy_kernel<double>, dim3(B), dim3(width), lds, (hipStream_t)stream,
-                           (const double*)scores, (long long)stride_t, (long long)stride_b, T, C, max_target_len, tg,
-                           (long long)target_stride, il, tl, blank, log_z, token_occ, onset, class_occ, expected_frames,
-                           onset_mean, aw);
+    XPS_CTC_LAUNCH(ctc_occupancy_kernel, dim3(B), dim3(occ_width(max_target_len)), lds, log_z, token_occ, onset, class_occ,
+                   expected_frames, onset_mean, aw);
     XPS_CHECK_LAUNCH();
     return XPS_OK;
 }

@@ -7,8 +7,11 @@
 // Tie rule, on D alone: walking back from (m, n), at i > 0 and j > 0 take the diagonal if D[i][j] == D[i-1][j-1] + [a_i != t_j],
 // else the insertion (i-1, j) if D[i][j] == D[i-1][j] + 1, else the deletion (i, j-1); i = 0: deletions, j = 0: insertions.
 //
-// The forward pass is edit_distance_kernel's (xps_ctc_data.hip): the target across the lanes in NCH register chunks of 64
-// columns, the in-row dependency removed by a wave prefix minimum.  Where it has D[i-1][j-1], D[i-1][j] and D[i][j] of a cell
+// The forward pass, edit_align_pair<NCH, WALK>, is written once for both entries: the target across the lanes in NCH register
+// chunks of 64 columns, 64 prediction tokens per load, the in-row dependency cur[j] = min(tmp[j], cur[j-1] + 1) removed by
+// the prefix minimum cur[j] = j + min_{k <= j}(tmp[k] - k), a 6-step wave scan.  xps_edit_distance_i64 launches it with
+// WALK = false (edit_distance_kernel: the row pass and dist[b], no other store), and so does xps_edit_align when dist is
+// the only output asked for.  With WALK = true, where it has D[i-1][j-1], D[i-1][j] and D[i][j] of a cell
 // at hand it evaluates the tie rule and stores the cell's backpointer byte (0 hit, 1 substitution, 2 insertion, 3 deletion):
 // 64 consecutive bytes per row and chunk.  Lane 0 then walks at most m + n dependent byte loads back from (m, n) and writes
 // the maps, the counts and the confusion adds; the -2 padding of the maps is stored by all lanes before the forward pass, so
@@ -23,7 +26,7 @@
 
 namespace {
 constexpr int EA_BIG = 1 << 29;
-constexpr int EA_MAX_PRED = 65536, EA_MAX_TGT = 1024;      // xps_edit_distance_supported
+constexpr int EA_MAX_PRED = 65536, EA_MAX_TGT = 1024;      // xps_edit_distance_supported: the caps of both entries
 constexpr int EA_BIN_CELLS = 8192;                         // confusion cells a workgroup sums in LDS: 32 KB, K <= 89
 
 __device__ inline int ea_prefix_min(int v, int lane) {
@@ -42,13 +45,14 @@ __device__ inline void ea_count(unsigned long long* conf, unsigned int* hist, in
     else atomicAdd(conf + cell, 1ull);
 }
 
-// One pair, by one wave.  bp: the pair's P * L backpointer bytes in the workspace; hist: the workgroup's confusion bins in
-// LDS, or NULL when the adds go straight to `conf`.
-template <int NCH>
+// One pair, by one wave.  WALK: keep the backpointers and walk them back; without it the row pass alone runs, dist[b] is
+// the only store and nothing from K on is looked at.  bp: the pair's P * L backpointer bytes in the workspace; hist: the
+// workgroup's confusion bins in LDS, or NULL when the adds go straight to `conf`.
+template <int NCH, bool WALK>
 __device__ inline void edit_align_pair(const long long* __restrict__ pred, long long pred_stride,
                                        const long long* __restrict__ pred_len, const long long* __restrict__ tgt,
                                        long long tgt_stride, const long long* __restrict__ tgt_len, int b, int lane, int P, int L,
-                                       int K, long long* __restrict__ dist, long long* __restrict__ counts,
+                                       long long* __restrict__ dist, int K, long long* __restrict__ counts,
                                        int* __restrict__ tgt_to_pred, int* __restrict__ pred_to_tgt,
                                        unsigned long long* __restrict__ conf, unsigned int* hist, unsigned char* bp) {
     long long ml = pred_len[b], nl = tgt_len[b];
@@ -56,9 +60,8 @@ __device__ inline void edit_align_pair(const long long* __restrict__ pred, long 
     const int n = nl < 0 ? 0 : (nl > L ? L : (int)nl);
     const long long* a = pred + (long long)b * pred_stride;
     const long long* t = tgt + (long long)b * tgt_stride;
-    int* t2p = tgt_to_pred ? tgt_to_pred + (long long)b * L : nullptr;
-    int* p2t = pred_to_tgt ? pred_to_tgt + (long long)b * P : nullptr;
-    const bool walk = counts || t2p || p2t || conf;                      // dist alone: no backpointers, no walk
+    int* t2p = WALK && tgt_to_pred ? tgt_to_pred + (long long)b * L : nullptr;
+    int* p2t = WALK && pred_to_tgt ? pred_to_tgt + (long long)b * P : nullptr;
     if (t2p)
         for (int j = n + lane; j < L; j += 64) t2p[j] = -2;
     if (p2t)
@@ -79,7 +82,7 @@ __device__ inline void edit_align_pair(const long long* __restrict__ pred, long 
         for (int r = 0; r < rows; ++r) {
             const long long tok = __shfl(mine, r, 64);
             const int i = i0 + r + 1;
-            unsigned char* row = bp + (i - 1) * L;                       // (i - 1) * L < 2^26
+            unsigned char* row = WALK ? bp + (i - 1) * L : nullptr;      // (i - 1) * L < 2^26
             int diag = i - 1;                                            // D[i-1][64 c]   (column before the chunk)
             int left = i;                                                // D[i][64 c]
 #pragma unroll
@@ -98,7 +101,7 @@ __device__ inline void edit_align_pair(const long long* __restrict__ pred, long 
                     diag = __shfl(up, 63, 64);
                     left = __shfl(cur, 63, 64);
                     prev[c] = j <= n ? cur : j;
-                    if (walk && j <= n)                                  // the tie rule, on D[i][j], D[i-1][j-1], D[i-1][j]
+                    if (WALK && j <= n)                                  // the tie rule, on D[i][j], D[i-1][j-1], D[i-1][j]
                         row[j - 1] = (unsigned char)(cur == sub ? neq : (cur == up + 1 ? 2 : 3));
                 }
             }
@@ -114,7 +117,7 @@ __device__ inline void edit_align_pair(const long long* __restrict__ pred, long 
         res = __shfl(val, l_last, 64);
     }
     if (lane == 0) dist[b] = res;
-    if (!walk) return;
+    if (!WALK) return;
     __threadfence_block();                                               // the wave's own backpointer stores, before lane 0 reads them
     if (lane != 0) return;
     // ---- the walk back from (m, n): one lane, at most m + n dependent byte loads ----
@@ -152,12 +155,24 @@ __device__ inline void edit_align_pair(const long long* __restrict__ pred, long 
     }
 }
 
+// 4 waves, 4 pairs: the row pass alone.
+template <int NCH>
+__global__ __launch_bounds__(256) void edit_distance_kernel(const long long* __restrict__ pred, long long pred_stride,
+                                                            const long long* __restrict__ pred_len, const long long* __restrict__ tgt,
+                                                            long long tgt_stride, const long long* __restrict__ tgt_len, int B,
+                                                            int P, int L, long long* __restrict__ dist) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b < B)
+        edit_align_pair<NCH, false>(pred, pred_stride, pred_len, tgt, tgt_stride, tgt_len, b, threadIdx.x & 63, P, L, dist, 0,
+                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
 // 4 waves, 4 pairs.  Dynamic LDS: `bins` confusion counters of the workgroup (0: none).
 template <int NCH>
 __global__ __launch_bounds__(256) void edit_align_kernel(const long long* __restrict__ pred, long long pred_stride,
                                                          const long long* __restrict__ pred_len, const long long* __restrict__ tgt,
                                                          long long tgt_stride, const long long* __restrict__ tgt_len, int B,
-                                                         int P, int L, int K, long long* __restrict__ dist,
+                                                         int P, int L, long long* __restrict__ dist, int K,
                                                          long long* __restrict__ counts, int* __restrict__ tgt_to_pred,
                                                          int* __restrict__ pred_to_tgt, unsigned long long* __restrict__ conf,
                                                          unsigned char* __restrict__ ws, int bins) {
@@ -170,8 +185,8 @@ __global__ __launch_bounds__(256) void edit_align_kernel(const long long* __rest
         __syncthreads();
     }
     if (b < B) {                                                         // a whole wave at a time: no divergence at the barriers
-        edit_align_pair<NCH>(pred, pred_stride, pred_len, tgt, tgt_stride, tgt_len, b, lane, P, L, K, dist, counts, tgt_to_pred,
-                             pred_to_tgt, conf, hist, ws + (size_t)b * (size_t)P * (size_t)L);
+        edit_align_pair<NCH, true>(pred, pred_stride, pred_len, tgt, tgt_stride, tgt_len, b, lane, P, L, dist, K, counts,
+                                   tgt_to_pred, pred_to_tgt, conf, hist, ws + (size_t)b * (size_t)P * (size_t)L);
     }
     if (bins) {                                                          // one add per non-zero cell and workgroup, 64 cells per
         __syncthreads();                                                 // wave-instruction: 4 pairs' steps cost a few instructions
@@ -181,6 +196,21 @@ __global__ __launch_bounds__(256) void edit_align_kernel(const long long* __rest
         }
     }
 }
+
+// KERNEL<NCH> for the padded target extent, 4 pairs per workgroup, over the entry's own arguments up to dist, then the
+// kernel's further arguments
+#define XPS_EDIT_LAUNCH_NCH(KERNEL, NCH, lds, ...)                                                                            \
+    hipLaunchKernelGGL(KERNEL<NCH>, dim3(cdiv(B, 4)), dim3(256), lds, (hipStream_t)stream,                                    \
+                       reinterpret_cast<const long long*>(pred), (long long)pred_stride,                                      \
+                       reinterpret_cast<const long long*>(pred_len), reinterpret_cast<const long long*>(tgt),                 \
+                       (long long)tgt_stride, reinterpret_cast<const long long*>(tgt_len), B, max_pred_len, max_tgt_len,      \
+                       reinterpret_cast<long long*>(dist), ##__VA_ARGS__)
+#define XPS_EDIT_LAUNCH(KERNEL, lds, ...)                                                                                     \
+    do {                                                                                                                      \
+        if (max_tgt_len <= 64) XPS_EDIT_LAUNCH_NCH(KERNEL, 1, lds, ##__VA_ARGS__);                                            \
+        else if (max_tgt_len <= 256) XPS_EDIT_LAUNCH_NCH(KERNEL, 4, lds, ##__VA_ARGS__);                                      \
+        else XPS_EDIT_LAUNCH_NCH(KERNEL, 16, lds, ##__VA_ARGS__);                                                             \
+    } while (0)
 }  // namespace
 
 extern "C" size_t xps_edit_align_workspace(int B, int max_pred_len, int max_tgt_len) {
@@ -188,39 +218,47 @@ extern "C" size_t xps_edit_align_workspace(int B, int max_pred_len, int max_tgt_
     return (size_t)B * (size_t)max_pred_len * (size_t)max_tgt_len + 16;
 }
 
+extern "C" int xps_edit_distance_supported(int max_pred_len, int max_tgt_len) {
+    return max_pred_len >= 0 && max_pred_len <= EA_MAX_PRED && max_tgt_len >= 0 && max_tgt_len <= EA_MAX_TGT;
+}
+
+extern "C" int xps_edit_distance_i64(const int64_t* pred, int64_t pred_stride, const int64_t* pred_len, const int64_t* tgt,
+                                     int64_t tgt_stride, const int64_t* tgt_len, int B, int max_pred_len, int max_tgt_len,
+                                     int64_t* dist, void* stream) {
+    XPS_CHECK_ARG(B >= 0, "bad argument");
+    XPS_CHECK_ARG(xps_edit_distance_supported(max_pred_len, max_tgt_len), "sequence lengths outside the supported range");
+    XPS_CHECK_ARG(pred_stride >= max_pred_len && tgt_stride >= max_tgt_len, "row stride shorter than the padded length");
+    if (B == 0) return XPS_OK;
+    XPS_CHECK_ARG(pred_len && tgt_len && dist, "null argument");
+    XPS_CHECK_ARG((pred || max_pred_len == 0) && (tgt || max_tgt_len == 0), "null argument");
+    XPS_EDIT_LAUNCH(edit_distance_kernel, 0);
+    XPS_CHECK_LAUNCH();
+    return XPS_OK;
+}
+
 extern "C" int xps_edit_align(const int64_t* pred, int64_t pred_stride, const int64_t* pred_len, const int64_t* tgt,
                               int64_t tgt_stride, const int64_t* tgt_len, int B, int max_pred_len, int max_tgt_len,
                               int n_classes, int64_t* dist, int64_t* counts, int32_t* tgt_to_pred, int32_t* pred_to_tgt,
                               int64_t* confusion, void* workspace, size_t workspace_bytes, void* stream) {
     XPS_CHECK_ARG(B >= 0, "bad argument");
-    XPS_CHECK_ARG(max_pred_len >= 0 && max_pred_len <= EA_MAX_PRED && max_tgt_len >= 0 && max_tgt_len <= EA_MAX_TGT,
-                  "sequence lengths outside the supported range");
+    XPS_CHECK_ARG(xps_edit_distance_supported(max_pred_len, max_tgt_len), "sequence lengths outside the supported range");
     XPS_CHECK_ARG(pred_stride >= max_pred_len && tgt_stride >= max_tgt_len, "row stride shorter than the padded length");
     XPS_CHECK_ARG(!confusion || n_classes >= 1, "a confusion matrix needs at least one class");
     if (B == 0) return XPS_OK;
     XPS_CHECK_ARG(pred_len && tgt_len && dist, "null argument");
     XPS_CHECK_ARG((pred || max_pred_len == 0) && (tgt || max_tgt_len == 0), "null argument");
     XPS_CHECK_ARG(workspace && workspace_bytes >= xps_edit_align_workspace(B, max_pred_len, max_tgt_len), "workspace too small");
-    const long long* p = reinterpret_cast<const long long*>(pred);
-    const long long* pl = reinterpret_cast<const long long*>(pred_len);
-    const long long* t = reinterpret_cast<const long long*>(tgt);
-    const long long* tl = reinterpret_cast<const long long*>(tgt_len);
-    long long* d = reinterpret_cast<long long*>(dist);
+    if (!counts && !tgt_to_pred && !pred_to_tgt && !confusion) {        // dist alone: no backpointers, no walk
+        XPS_EDIT_LAUNCH(edit_distance_kernel, 0);
+        XPS_CHECK_LAUNCH();
+        return XPS_OK;
+    }
     long long* cn = reinterpret_cast<long long*>(counts);
     unsigned long long* cf = reinterpret_cast<unsigned long long*>(confusion);
     unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-    const dim3 grid(cdiv(B, 4)), block(256);
     const long long conf_cells = ((long long)n_classes + 1) * ((long long)n_classes + 1);
     const int bins = confusion && conf_cells <= EA_BIN_CELLS ? (int)conf_cells : 0;
-    const size_t bin_bytes = sizeof(unsigned int) * (size_t)bins;
-#define XPS_EA_LAUNCH(NCH)                                                                                                      \
-    hipLaunchKernelGGL(edit_align_kernel<NCH>, grid, block, bin_bytes, (hipStream_t)stream, p, (long long)pred_stride, pl, t,     \
-                       (long long)tgt_stride, tl, B, max_pred_len, max_tgt_len, n_classes, d, cn, tgt_to_pred, pred_to_tgt, cf,  \
-                       ws, bins)
-    if (max_tgt_len <= 64) XPS_EA_LAUNCH(1);
-    else if (max_tgt_len <= 256) XPS_EA_LAUNCH(4);
-    else XPS_EA_LAUNCH(16);
-#undef XPS_EA_LAUNCH
+    XPS_EDIT_LAUNCH(edit_align_kernel, sizeof(unsigned int) * (size_t)bins, n_classes, cn, tgt_to_pred, pred_to_tgt, cf, ws, bins);
     XPS_CHECK_LAUNCH();
     return XPS_OK;
 }

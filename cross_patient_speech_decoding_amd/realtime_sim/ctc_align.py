@@ -2,13 +2,11 @@
 (csrc/xps_ctc_align.hip), i.e. when each phoneme was emitted.  One launch for the batch, float64
 additions and comparisons only, so the result is bit for bit the recursion of include/xps.h.  There is no CPU fallback;
 the shape and range checks run before any device call."""
-import numpy as np
 import torch
 
-from .._dev import current_device, ptr, stream, workspace
+from .._dev import ptr, stream, workspace
 from .._lib import call, lib
-
-TARGET_MAX = 511                    # 2 * L + 1 <= 1023 states, the CTC loss kernel's cap (include/xps.h)
+from ._ctc_host import TARGET_MAX, check_lattice_inputs, frame_times, lattice_on_device  # noqa: F401
 
 
 class CTCAlignment:
@@ -46,12 +44,7 @@ class CTCAlignment:
         """Spans mapped through a per-frame time vector: frame_time (T,), the time of each frame (window_end_times for the
         realtime model's windows) -> (onset, offset) (B, Lmax) tensors of frame_time's dtype on the device, onset the time of
         a token's first frame and offset the time of its LAST frame (end - 1); NaN where there is no span."""
-        ft = torch.as_tensor(frame_time)
-        if not ft.is_floating_point():
-            ft = ft.double()
-        ft = ft.to(self.states.device).reshape(-1)
-        if ft.numel() != self.states.shape[1]:
-            raise ValueError(f'{ft.numel()} frame times for {self.states.shape[1]} frames')
+        ft = frame_times(frame_time, self.states.shape[1], self.states.device)
         none = self.token_start < 0
         if ft.numel() == 0:
             nan = torch.full(self.token_start.shape, float('nan'), dtype=ft.dtype, device=ft.device)
@@ -72,66 +65,6 @@ def window_end_times(n_windows, win_size, stride, step_s):
     return (idx[:, -1] + 1).double() * float(step_s)
 
 
-def _lengths(v, B, top, what):
-    if v is None:
-        return None
-    v = torch.as_tensor(v)
-    host = v.detach().cpu().to(torch.int64).reshape(-1)
-    if host.numel() != B:
-        raise ValueError(f'{host.numel()} {what} for {B} sequences')
-    if B and (int(host.min()) < 0 or int(host.max()) > top):
-        raise ValueError(f'{what} outside 0..{top}')
-    return host
-
-
-def _check(scores, targets, input_lengths, target_lengths, blank, time_major):
-    """Every shape and range check of forced_align, on the host.  Returns (scores, targets (B, Lmax) int64 host or device
-    tensor, input_lengths, target_lengths (host int64 or None), T, B, C)."""
-    scores = torch.as_tensor(scores)
-    if scores.dim() != 3:
-        raise ValueError(f'scores of shape {tuple(scores.shape)}: expected three axes')
-    (T, B) = (scores.size(0), scores.size(1)) if time_major else (scores.size(1), scores.size(0))
-    Cn = scores.size(2)
-    if Cn < 1:
-        raise ValueError('forced alignment needs at least one class')
-    if not 0 <= int(blank) < Cn:
-        raise ValueError(f'blank {blank} outside 0..{Cn - 1}')
-    if isinstance(targets, (list, tuple)) and not (len(targets) and all(np.ndim(t) == 0 for t in targets)):
-        rows = [torch.as_tensor(t).detach().cpu().to(torch.int64) for t in targets]
-        if any(r.dim() != 1 for r in rows):
-            raise ValueError('a list of targets holds 1-D sequences')
-        if target_lengths is not None:
-            raise ValueError('a list of targets carries its own lengths: target_lengths must be None')
-        if len(rows) != B:
-            raise ValueError(f'{len(rows)} targets for {B} sequences')
-        Lmax = max([r.numel() for r in rows], default=0)
-        target_lengths = torch.tensor([r.numel() for r in rows], dtype=torch.int64)
-        targets = torch.zeros(B, Lmax, dtype=torch.int64)
-        for b, r in enumerate(rows):
-            targets[b, :r.numel()] = r
-    else:
-        targets = torch.as_tensor(targets)
-        if targets.dim() != 2:
-            raise ValueError(f'targets of shape {tuple(targets.shape)}: expected (B, Lmax) or a list of 1-D sequences')
-        if targets.is_floating_point() or targets.dtype == torch.bool:
-            raise ValueError(f'targets of dtype {targets.dtype}: expected integers')
-        if targets.size(0) != B:
-            raise ValueError(f'{targets.size(0)} targets for {B} sequences')
-    Lmax = targets.size(1)
-    if Lmax > TARGET_MAX:
-        raise ValueError(f'targets of {Lmax} labels: the alignment kernel holds at most {TARGET_MAX}')
-    il = _lengths(input_lengths, B, T, 'input_lengths')
-    tl = _lengths(target_lengths, B, Lmax, 'target_lengths')
-    host = targets.detach().cpu().to(torch.int64)
-    if B and Lmax:
-        live = torch.arange(Lmax)[None, :] < (tl[:, None] if tl is not None else Lmax)
-        bad = live & ((host < 0) | (host >= Cn))
-        if bool(bad.any()):
-            b, j = (int(v) for v in bad.nonzero()[0])
-            raise ValueError(f'target {b} holds the label {int(host[b, j])} at position {j}: outside 0..{Cn - 1}')
-    return scores, targets, il, tl, T, B, Cn
-
-
 def forced_align(scores, targets, input_lengths=None, target_lengths=None, blank=0, time_major=False):
     """Best CTC path of each sequence's target through its scores -> CTCAlignment.  scores (B, T, C), or (T, B, C) with
     time_major: float32 / float64 scores of any kind (no softmax is applied: a per-frame constant shifts every path
@@ -140,25 +73,16 @@ def forced_align(scores, targets, input_lengths=None, target_lengths=None, blank
     targets (B, Lmax) integers padded, with target_lengths (B,) (None: all Lmax), or a list of B 1-D sequences;
     input_lengths (B,) (None: all T).  Lengths and labels are checked here, on the host (a device tensor of targets or
     lengths is copied to the host for it, which waits for it); every check raises ValueError before any device call."""
-    scores, targets, il, tl, T, B, Cn = _check(scores, targets, input_lengths, target_lengths, blank, time_major)
-    dev = scores.device if scores.is_cuda else current_device('forced_align')
-    if scores.dtype not in (torch.float32, torch.float64):
-        scores = scores.float() if scores.is_floating_point() else scores.double()
-    scores = scores.to(dev)
-    if Cn > 1 and scores.stride(2) != 1:
-        scores = scores.contiguous()
-    st, sb = (scores.stride(0), scores.stride(1)) if time_major else (scores.stride(1), scores.stride(0))
-    Lmax = targets.size(1)
-    tg = targets.to(dev, torch.int64).contiguous()
-    il_d = None if il is None else il.to(dev)
-    tl_d = torch.full((B,), Lmax, dtype=torch.int64, device=dev) if tl is None else tl.to(dev)
+    scores, targets, il, tl, T, B, Cn = check_lattice_inputs(scores, targets, input_lengths, target_lengths, blank, time_major)
+    d = lattice_on_device(scores, targets, il, tl, time_major, 'forced_align')
+    dev, Lmax = d.device, targets.size(1)
     states = torch.empty(B, T, dtype=torch.int32, device=dev)
     t0 = torch.empty(B, Lmax, dtype=torch.int32, device=dev)
     t1 = torch.empty(B, Lmax, dtype=torch.int32, device=dev)
     score = torch.empty(B, dtype=torch.float64, device=dev)
     ws_bytes = int(lib().xps_ctc_align_workspace(B, T, Lmax))
     ws = workspace(ws_bytes, dev)
-    call('xps_ctc_align', scores.data_ptr(), int(scores.dtype == torch.float32), int(st), int(sb), T, B, Cn, Lmax,
-         tg.data_ptr(), Lmax, ptr(il_d), tl_d.data_ptr(), int(blank), states.data_ptr(), t0.data_ptr(), t1.data_ptr(),
+    call('xps_ctc_align', d.scores.data_ptr(), d.is_f32, d.stride_t, d.stride_b, T, B, Cn, Lmax, d.targets.data_ptr(), Lmax,
+         ptr(d.input_lengths), d.target_lengths.data_ptr(), int(blank), states.data_ptr(), t0.data_ptr(), t1.data_ptr(),
          score.data_ptr(), ws.data_ptr(), ws_bytes, stream(dev))
-    return CTCAlignment(states, t0, t1, score, tg, tl_d, blank)
+    return CTCAlignment(states, t0, t1, score, d.targets, d.target_lengths, blank)

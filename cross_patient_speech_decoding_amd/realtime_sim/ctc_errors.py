@@ -7,9 +7,8 @@ import torch
 
 from .._dev import ptr, stream, workspace
 from .._lib import call, lib
-from .ctc_align import _lengths
+from ._ctc_host import EDIT_MAX_PRED, EDIT_MAX_TARGET, at, integer_tokens, labels_in_range, lengths, runs_within
 
-MAX_PRED, MAX_TARGET = 65536, 1024            # xps_edit_distance_supported (include/xps.h)
 MAX_WORKSPACE_BYTES = 1 << 30
 OPS = ('hit', 'substitution', 'deletion', 'insertion')
 
@@ -105,55 +104,29 @@ class EditAlignment:
 def workspace_runs(B, P, L, max_workspace_bytes):
     """Cut B pairs into runs [(start, stop), ...] whose backpointer workspace, P * L bytes per pair, stays within
     max_workspace_bytes; as few runs as that allows, of even size.  A single pair above the limit raises ValueError."""
-    per = max(int(P), 0) * max(int(L), 0)
-    if B <= 0:
-        return []
-    if per > int(max_workspace_bytes):
-        raise ValueError(f'one pair of up to {P} against {L} tokens needs {per} bytes of workspace: '
-                         f'above max_workspace_bytes = {int(max_workspace_bytes)}')
-    most = B if per == 0 else min(B, int(max_workspace_bytes) // per)
-    n = -(-B // -(-B // most))                      # the fewest runs, then evened out: no short last launch
-    return [(s, min(s + n, B)) for s in range(0, B, n)]
-
-
-def _tokens(v, what):
-    v = torch.as_tensor(v)
-    if v.dim() != 2:
-        raise ValueError(f'{what} of shape {tuple(v.shape)}: expected two axes, (B, {"P" if what == "pred" else "L"})')
-    if v.is_floating_point() or v.dtype == torch.bool:
-        raise ValueError(f'{what} of dtype {v.dtype}: expected integers')
-    return v
-
-
-def _labels_in_range(host, lens, K, what):
-    width = host.size(1)
-    if host.size(0) and width:
-        live = torch.arange(width)[None, :] < lens[:, None]
-        bad = live & ((host < 0) | (host >= K))
-        if bool(bad.any()):
-            b, j = (int(v) for v in bad.nonzero()[0])
-            raise ValueError(f'{what} {b} holds the label {int(host[b, j])} at position {j}: outside 0..{K - 1}')
+    return runs_within(B, max(int(P), 0) * max(int(L), 0), max_workspace_bytes, f'one pair of up to {P} against {L} tokens')
 
 
 def _check(pred, pred_lengths, targets, target_lengths, n_classes, max_workspace_bytes):
     """Every shape, length and label check of edit_align, on the host.  Returns (pred, targets, pred_lengths, target_lengths
     (host int64), runs)."""
-    pred, targets = _tokens(pred, 'pred'), _tokens(targets, 'targets')
+    pred, targets = integer_tokens(pred, 'pred', 'two axes, (B, P)'), integer_tokens(targets, 'targets', 'two axes, (B, L)')
     if pred.size(0) != targets.size(0):
         raise ValueError(f'{pred.size(0)} predictions for {targets.size(0)} targets')
     B, P, L = pred.size(0), pred.size(1), targets.size(1)
-    if P > MAX_PRED or L > MAX_TARGET:
-        raise ValueError(f'edit alignment of up to {P} against {L} tokens: the kernel supports {MAX_PRED} against {MAX_TARGET}')
+    if P > EDIT_MAX_PRED or L > EDIT_MAX_TARGET:
+        raise ValueError(f'edit alignment of up to {P} against {L} tokens: the kernel supports {EDIT_MAX_PRED} against '
+                         f'{EDIT_MAX_TARGET}')
     if pred_lengths is None:
         raise ValueError('pred_lengths is needed: the padding of a decode carries no length')
-    pl = _lengths(pred_lengths, B, P, 'pred_lengths')
-    tl = torch.full((B,), L, dtype=torch.int64) if target_lengths is None else _lengths(target_lengths, B, L, 'target_lengths')
+    pl = lengths(pred_lengths, B, P, 'pred_lengths')
+    tl = torch.full((B,), L, dtype=torch.int64) if target_lengths is None else lengths(target_lengths, B, L, 'target_lengths')
     if n_classes is not None:
         K = int(n_classes)
         if K < 1:
             raise ValueError(f'n_classes {n_classes}: a confusion matrix needs at least one class')
-        _labels_in_range(pred.detach().cpu().to(torch.int64), pl, K, 'prediction')
-        _labels_in_range(targets.detach().cpu().to(torch.int64), tl, K, 'target')
+        labels_in_range(pred.detach().cpu().to(torch.int64), pl, K, 'prediction')
+        labels_in_range(targets.detach().cpu().to(torch.int64), tl, K, 'target')
     return pred, targets, pl, tl, workspace_runs(B, P, L, max_workspace_bytes)
 
 
@@ -185,11 +158,8 @@ def edit_align(pred, pred_lengths, targets, target_lengths, n_classes=None, max_
     conf = None if n_classes is None else torch.zeros(K + 1, K + 1, dtype=torch.int64, device=dev)
     ws_bytes = max([int(lib().xps_edit_align_workspace(b1 - b0, P, L)) for b0, b1 in runs], default=0)
     ws = workspace(ws_bytes, dev)
-
-    def at(t, b0, row, item=8):
-        return t.data_ptr() + item * b0 * row
     for b0, b1 in runs:
         call('xps_edit_align', at(pred, b0, P), P, at(pl_d, b0, 1), at(targets, b0, L), L, at(tl_d, b0, 1), b1 - b0, P, L, K,
-             at(dist, b0, 1), at(counts, b0, 4), at(t2p, b0, L, 4), at(p2t, b0, P, 4), ptr(conf), ws.data_ptr(), ws_bytes,
+             at(dist, b0, 1), at(counts, b0, 4), at(t2p, b0, L), at(p2t, b0, P), ptr(conf), ws.data_ptr(), ws_bytes,
              stream(dev))
     return EditAlignment(dist, counts, t2p, p2t, conf, pred, pl_d, targets, tl_d)

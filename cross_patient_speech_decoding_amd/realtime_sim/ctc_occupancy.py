@@ -4,9 +4,9 @@ started at, a frame -- where forced_align reports the one best path.  Float64 in
 include/xps.h.  There is no CPU fallback; the shape and range checks (forced_align's own) run before any device call."""
 import torch
 
-from .._dev import current_device, ptr, stream, workspace
+from .._dev import ptr, stream, workspace
 from .._lib import call, lib
-from .ctc_align import _check
+from ._ctc_host import at, check_lattice_inputs, frame_times, lattice_on_device, runs_within
 
 WANT = ('token_occ', 'onset', 'class_occ')
 MAX_WORKSPACE_BYTES = 1 << 30
@@ -39,12 +39,7 @@ class CTCOccupancy:
         the realtime model's windows) -> (mean, sd) (B, Lmax) tensors of frame_time's dtype on the device: the mean and the
         standard deviation of each token's onset time under `onset`; NaN where there is no token."""
         onset = self._need('onset')
-        ft = torch.as_tensor(frame_time)
-        if not ft.is_floating_point():
-            ft = ft.double()
-        ft = ft.to(onset.device).reshape(-1)
-        if ft.numel() != onset.shape[1]:
-            raise ValueError(f'{ft.numel()} frame times for {onset.shape[1]} frames')
+        ft = frame_times(frame_time, onset.shape[1], onset.device)
         w = onset.to(ft.dtype)
         mean = (w * ft[None, :, None]).sum(1)
         var = (w * (ft[None, :, None] - mean[:, None, :]) ** 2).sum(1)
@@ -68,15 +63,8 @@ def workspace_runs(B, T, Lmax, max_workspace_bytes):
     """Cut B sequences into runs [(start, stop), ...] whose alpha workspace, T * (2 Lmax + 1) * 8 bytes per sequence, stays
     within max_workspace_bytes; as few runs as that allows, of even size.  A single sequence above the limit raises
     ValueError."""
-    per = max(int(T), 0) * (2 * int(Lmax) + 1) * 8
-    if B <= 0:
-        return []
-    if per > int(max_workspace_bytes):
-        raise ValueError(f'one sequence of {T} frames and {Lmax} labels needs {per} bytes of workspace: '
-                         f'above max_workspace_bytes = {int(max_workspace_bytes)}')
-    most = B if per == 0 else min(B, int(max_workspace_bytes) // per)
-    n = -(-B // -(-B // most))                      # the fewest runs, then evened out: no short last launch
-    return [(s, min(s + n, B)) for s in range(0, B, n)]
+    return runs_within(B, max(int(T), 0) * (2 * int(Lmax) + 1) * 8, max_workspace_bytes,
+                       f'one sequence of {T} frames and {Lmax} labels')
 
 
 def posterior_align(scores, targets, input_lengths=None, target_lengths=None, blank=0, time_major=False,
@@ -96,19 +84,11 @@ def posterior_align(scores, targets, input_lengths=None, target_lengths=None, bl
     unknown = [w for w in want if w not in WANT]
     if unknown:
         raise ValueError(f'want holds {unknown[0]!r}: expected a subset of {WANT}')
-    scores, targets, il, tl, T, B, Cn = _check(scores, targets, input_lengths, target_lengths, blank, time_major)
+    scores, targets, il, tl, T, B, Cn = check_lattice_inputs(scores, targets, input_lengths, target_lengths, blank, time_major)
     Lmax = targets.size(1)
     runs = workspace_runs(B, T, Lmax, max_workspace_bytes)
-    dev = scores.device if scores.is_cuda else current_device('posterior_align')
-    if scores.dtype not in (torch.float32, torch.float64):
-        scores = scores.float() if scores.is_floating_point() else scores.double()
-    scores = scores.to(dev)
-    if Cn > 1 and scores.stride(2) != 1:
-        scores = scores.contiguous()
-    st, sb = (scores.stride(0), scores.stride(1)) if time_major else (scores.stride(1), scores.stride(0))
-    tg = targets.to(dev, torch.int64).contiguous()
-    il_d = None if il is None else il.to(dev)
-    tl_d = torch.full((B,), Lmax, dtype=torch.int64, device=dev) if tl is None else tl.to(dev)
+    d = lattice_on_device(scores, targets, il, tl, time_major, 'posterior_align')
+    dev = d.device
 
     def out(*shape):
         return torch.empty(*shape, dtype=torch.float64, device=dev)
@@ -118,13 +98,9 @@ def posterior_align(scores, targets, input_lengths=None, target_lengths=None, bl
     cls = out(B, T, Cn) if 'class_occ' in want else None
     ws_bytes = max([int(lib().xps_ctc_occupancy_workspace(b1 - b0, T, Lmax)) for b0, b1 in runs], default=0)
     ws = workspace(ws_bytes, dev)
-    item = scores.element_size()
-
-    def at(t, b0, row):
-        return None if t is None else t.data_ptr() + 8 * b0 * row
     for b0, b1 in runs:
-        call('xps_ctc_occupancy', scores.data_ptr() + item * b0 * int(sb), int(scores.dtype == torch.float32), int(st),
-             int(sb), T, b1 - b0, Cn, Lmax, at(tg, b0, Lmax), Lmax, at(il_d, b0, 1), at(tl_d, b0, 1), int(blank),
+        call('xps_ctc_occupancy', at(d.scores, b0, d.stride_b), d.is_f32, d.stride_t, d.stride_b, T, b1 - b0, Cn, Lmax,
+             at(d.targets, b0, Lmax), Lmax, at(d.input_lengths, b0, 1), at(d.target_lengths, b0, 1), int(blank),
              at(log_z, b0, 1), at(tok, b0, T * Lmax), at(ons, b0, T * Lmax), at(cls, b0, T * Cn), at(ef, b0, Lmax),
              at(om, b0, Lmax), ptr(ws), ws_bytes, stream(dev))
-    return CTCOccupancy(log_z, tok, ons, cls, ef, om, tg, tl_d, blank)
+    return CTCOccupancy(log_z, tok, ons, cls, ef, om, d.targets, d.target_lengths, blank)

@@ -20,6 +20,7 @@ from ..nn_models import functional as XF
 from ..nn_models._lightning import LightningModule
 from .._dev import current_device, stream
 from .._lib import call as _call, rowmap  # noqa: F401
+from ._ctc_host import EDIT_MAX_PRED, EDIT_MAX_TARGET
 from .ctc_align import forced_align
 from .ctc_occupancy import posterior_align
 from .ctc_decoder import greedy_decode_batch, greedy_decode_device  # noqa: F401
@@ -56,9 +57,6 @@ class _HipCTCLoss(nn.CTCLoss):
             return XF.ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=self.blank,
                                zero_infinity=self.zero_infinity)
         return super().forward(log_probs, targets, input_lengths, target_lengths)
-
-
-EDIT_MAX_PRED, EDIT_MAX_TARGET = 65536, 1024        # xps_edit_distance_supported (include/xps.h)
 
 
 def edit_distance_device(pred, pred_lengths, targets, target_lengths):

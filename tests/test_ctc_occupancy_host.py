@@ -269,7 +269,7 @@ def test_wrapper_refusals_need_no_device():
 
 def test_the_checks_are_forced_aligns_own():
     from cross_patient_speech_decoding_amd.realtime_sim import ctc_align, ctc_occupancy
-    assert ctc_occupancy._check is ctc_align._check
+    assert ctc_occupancy.check_lattice_inputs is ctc_align.check_lattice_inputs
 
 
 def test_workspace_runs_is_a_pure_function_of_the_sizes():

@@ -217,9 +217,21 @@ def test_guarded_buffers_strides_clamping_and_determinism(P, L):
     pred, pl, tgt, tl, ref, (B, K), m, n = _guarded_case(P, L)
     dev = [_dev(a) for a in (pred, pl, tgt, tl)]
     before = [t.clone() for t in dev]
-    dist_kernel = torch.empty(B, dtype=torch.int64, device='cuda')
+    # xps_edit_distance_i64 runs the row pass of a function that also holds the alignment's stores: dist, B int64 in the
+    # middle of a guarded buffer, is all it may write
+    gap = _Launch.GAP
+    dbuf = Buf(2 * B + 2 * gap)
     assert _lib().xps_edit_distance_i64(dev[0].data_ptr(), P + 3, dev[1].data_ptr(), dev[2].data_ptr(), L + 2,
-                                        dev[3].data_ptr(), B, P, L, dist_kernel.data_ptr(), _stream()) == 0
+                                        dev[3].data_ptr(), B, P, L, dbuf.ptr + 4 * gap, _stream()) == 0
+    torch.cuda.synchronize()
+    assert dbuf.guards_intact(), 'xps_edit_distance_i64 wrote a guard row'
+    dwords = dbuf.view().view(torch.int32).cpu().numpy()
+    assert (dwords[:gap] == np.int32(SENT)).all() and (dwords[gap + 2 * B:] == np.int32(SENT)).all(), \
+        'xps_edit_distance_i64 wrote outside dist'
+    dist_kernel = torch.from_numpy(dwords[gap:gap + 2 * B].view(np.int64).copy())
+    assert np.array_equal(dist_kernel.numpy(), ref[0])
+    for t, b4 in zip(dev, before):
+        assert torch.equal(t, b4), 'xps_edit_distance_i64 wrote an input'
     runs = []
     for _ in range(2):
         la = _Launch(B, P, L, K)
