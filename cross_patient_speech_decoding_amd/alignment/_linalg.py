@@ -1261,3 +1261,98 @@ def tsne_descent(problems, n_launches, max_iter, momentum, exaggeration, n_iter_
     n_launches & 1."""
     return _tsne_call('xps_tsne_descent_f64', problems, int(n_launches), int(max_iter), float(momentum), float(exaggeration),
                       int(n_iter_without_progress), float(min_grad_norm))
+
+
+# ------------------------------------------------------------------------------------ RDM analysis (csrc/xps_rsa.hip)
+RSA_STD_WORDS, RSA_RDM_WORDS, RSA_PAIR_WORDS = 8, 8, 12      # XPS_RSA_STD_WORDS, XPS_RSA_RDM_WORDS, XPS_RSA_PAIR_WORDS of include/xps.h
+RSA_MAX_CONDITIONS = 1024                                    # XPS_RSA_MAX_CONDITIONS
+# the words of a pair (include/xps.h)
+CP_A, CP_LDA, CP_NA, CP_IA, CP_B, CP_LDB, CP_NB, CP_IB, CP_M, CP_TABLE, CP_ROW = range(11)
+
+
+def _check_f64_matrix(t, what):
+    _check_matrix(t, what)
+    if t.dtype != F64:
+        raise ValueError(f'{what}: a float64 device matrix is needed')
+
+
+def _rows_call(name, tab, words):
+    """One row-per-workgroup call of csrc/xps_rsa.hip on the host table `tab`; returns what the caller keeps until it has
+    synchronised with the stream."""
+    tab = np.ascontiguousarray(tab.reshape(-1))
+    n = len(tab) // words
+    if n > 65535:
+        raise ValueError(f'{name}: {n} problems; at most 65535 go into one call')
+    nb = int(getattr(lib(), name + '_workspace')(n))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=device())
+    call(name, tab.ctypes.data, n, ws.data_ptr(), nb, stream())
+    return tab, ws
+
+
+def row_standardize_grouped(problems):
+    """problems: list of (X, Z): every row of Z becomes (x - mean) / |x - mean| of the row x of X (scipy.stats.pearsonr's
+    arithmetic; NaN for a constant row), for every problem in ONE xps_row_standardize_grouped_f64 launch.  X, Z (rows, D) float64
+    device matrices with contiguous rows, D >= 1; Z may be X.  Returns the host table and workspace of the call."""
+    if not problems:
+        return None
+    tab = np.zeros((len(problems), RSA_STD_WORDS), dtype=np.int64)
+    for i, (X, Z) in enumerate(problems):
+        _check_f64_matrix(X, 'row_standardize_grouped X')
+        _check_f64_matrix(Z, 'row_standardize_grouped Z')
+        if tuple(Z.shape) != tuple(X.shape) or X.shape[1] < 1 or X.shape[0] >= 2 ** 31 or X.shape[1] >= 2 ** 31:
+            raise ValueError('row_standardize_grouped: X and Z must be (rows, D) matrices of one shape with D >= 1')
+        tab[i, :6] = [X.data_ptr(), X.stride(0), X.shape[0], X.shape[1], Z.data_ptr(), Z.stride(0)]
+    return _rows_call('xps_row_standardize_grouped_f64', tab, RSA_STD_WORDS)
+
+
+def rdm_from_corr_grouped(problems):
+    """problems: list of (C, out): out[i][j] = 1 - clip(C[i][j], -1, 1), NaN kept, the diagonal exactly 0 unless it is NaN, for every
+    problem in ONE xps_rdm_from_corr_grouped_f64 launch.  C, out (n, n) float64 device matrices with contiguous rows; out may be C.
+    Returns the host table and workspace of the call."""
+    if not problems:
+        return None
+    tab = np.zeros((len(problems), RSA_RDM_WORDS), dtype=np.int64)
+    for i, (Cm, out) in enumerate(problems):
+        _check_f64_matrix(Cm, 'rdm_from_corr_grouped C')
+        _check_f64_matrix(out, 'rdm_from_corr_grouped out')
+        n = Cm.shape[0]
+        if tuple(Cm.shape) != (n, n) or tuple(out.shape) != (n, n) or n >= 2 ** 31:
+            raise ValueError('rdm_from_corr_grouped: C and out must be square matrices of one size')
+        tab[i, :5] = [Cm.data_ptr(), Cm.stride(0), n, out.data_ptr(), out.stride(0)]
+    return _rows_call('xps_rdm_from_corr_grouped_f64', tab, RSA_RDM_WORDS)
+
+
+def rdm_compare_perm(pairs, idx, tables, perms, R, cosine=False):
+    """The centred triangle products of pairs of RDMs under R relabellings of the second one: ONE xps_rdm_compare_perm_f64 call (two
+    launches).  pairs: list of (A, ia, B, ib, m, table): A, B square float64 device matrices with contiguous rows, ia / ib the
+    offsets in `idx` (int32 host array) of the m indices of the shared conditions in A / B, `table` the row of `tables` (int64
+    (n_tables, 2) host array of {offset in `perms`, m}) that holds the pair's (R + 1, m) int32 permutations, row 0 the identity.
+    Returns (stats (n_pairs, 4) = {mean_x, mean_y, sxx, syy}, cross (n_pairs, R + 1), keep): device tensors in pair order, and the
+    host tables and workspace of the call, which the caller keeps until it has synchronised with the stream.  The library checks
+    every index and every permutation before it launches."""
+    n, R = len(pairs), int(R)
+    idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+    perms = np.ascontiguousarray(perms, dtype=np.int32).reshape(-1)
+    tables = np.ascontiguousarray(tables, dtype=np.int64).reshape(-1, 2)
+    if R < 0:
+        raise ValueError(f'rdm_compare_perm: R must be non-negative; got {R}')
+    tab = np.zeros((n, RSA_PAIR_WORDS), dtype=np.int64)
+    for q, (A, ia, B, ib, m, table) in enumerate(pairs):
+        _check_f64_matrix(A, 'rdm_compare_perm A')
+        _check_f64_matrix(B, 'rdm_compare_perm B')
+        if A.shape[0] != A.shape[1] or B.shape[0] != B.shape[1] or A.shape[0] < 1 or B.shape[0] < 1:
+            raise ValueError('rdm_compare_perm: A and B must be square matrices')
+        if not 2 <= int(m) <= RSA_MAX_CONDITIONS:
+            raise ValueError(f'rdm_compare_perm: {int(m)} shared conditions; 2 to XPS_RSA_MAX_CONDITIONS = {RSA_MAX_CONDITIONS} are supported')
+        tab[q, :11] = [A.data_ptr(), A.stride(0), A.shape[0], ia, B.data_ptr(), B.stride(0), B.shape[0], ib, m, table, q]
+    dev = device()
+    stats = torch.empty(n, 4, dtype=F64, device=dev)
+    cross = torch.empty(n, R + 1, dtype=F64, device=dev)
+    if n == 0:
+        return stats, cross, None
+    tab = np.ascontiguousarray(tab.reshape(-1))
+    nb = int(lib().xps_rdm_compare_perm_f64_workspace(n, len(tables), len(idx), len(perms)))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=dev)
+    call('xps_rdm_compare_perm_f64', tab.ctypes.data, n, tables.ctypes.data, len(tables), idx.ctypes.data, len(idx), perms.ctypes.data,
+         len(perms), R, int(bool(cosine)), stats.data_ptr(), cross.data_ptr(), n, ws.data_ptr(), nb, stream())
+    return stats, cross, (tab, tables, idx, perms, ws)

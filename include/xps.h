@@ -1235,6 +1235,58 @@ int xps_tsne_descent_f64(const int64_t* problems, int n_problems, const int32_t*
                          double momentum, double exaggeration, int n_iter_without_progress, double min_grad_norm, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Representational dissimilarity analysis (csrc/xps_rsa.hip; alignment/rsa.py;   */
+/* DESIGN.md 4.23): the figure notebooks' calc_rdm_corr / compare_rdms, batched.   */
+/* ------------------------------------------------------------------------- */
+/* Every entry takes xps_gram_grouped_f64's convention: HOST tables of int64 words, checked by the call and copied into ws (DEVICE,
+ * ..._workspace(...) bytes) on the stream; they stay valid until the stream has passed the call.  Nothing allocates or
+ * synchronises; every refusal is XPS_E_INVALID before any launch.  Float64, no atomics; every sum is taken in an order that is a
+ * function of the problem alone (a thread or lane adds its elements in ascending order, the partial sums meet in a fixed tree),
+ * so a problem's bits do not depend on the grid, the stream or the other problems of the call.
+ *
+ * xps_row_standardize_grouped_f64: every row x of every problem's matrix X (rows x D, leading dimension ldx >= D) becomes
+ * z = (x - mean) / |x - mean| in Z (leading dimension ldz >= D; Z may be X), scipy.stats.pearsonr's arithmetic: the Gram matrix
+ * of Z holds every r_ij.  mean = m0 + sum(x - m0) / D with m0 = sum(x) / D; |.| = sqrt(sum d^2).  A row whose elements are all
+ * equal (scipy's constant input) and any row of norm 0 become NaN.  Words of a problem (XPS_RSA_STD_WORDS each): 0 X, 1 ldx,
+ * 2 rows, 3 D (>= 1), 4 Z, 5 ldz.  At most 65535 problems.  Refused: a null table or matrix, negative counts, D < 1, ldx < D,
+ * ldz < D, a null or too small workspace.
+ *
+ * xps_rdm_from_corr_grouped_f64: out[i][j] = 1 - clip(r[i][j], -1, 1) for every problem; a NaN stays a NaN; the diagonal is
+ * exactly 0 unless it is NaN.  Words of a problem (XPS_RSA_RDM_WORDS each): 0 r (n x n), 1 ldr (>= n), 2 n, 3 out (n x n; may be
+ * r), 4 ldo (>= n).  At most 65535 problems.  Refused: a null table or matrix, a negative n, ldr < n, ldo < n, a null or too
+ * small workspace.
+ *
+ * xps_rdm_compare_perm_f64: for every pair q of matrices (A, B) with index lists ia, ib of m shared conditions and for every row
+ * p of the pair's permutation table, over the upper triangle u < v in np.triu_indices order, x = A[ia[u]][ia[v]] and
+ * y_p = B[ib[p[u]]][ib[p[v]]]:
+ *     stats[row] = {mean_x, mean_y, sxx, syy} of x and y_identity (sums of squared deviations; cosine = 1: both means 0),
+ *     cross[row][r] = sum (x - mean_x) (y_p - mean_y) for row r of the table, r = 0 .. R.
+ * B must be symmetric: a relabelling then leaves the multiset of its triangle, and so mean_y and syy, unchanged.  The Pearson
+ * (cosine) similarity under permutation r is cross[row][r] / (sqrt(sxx) sqrt(syy)), taken by the caller.  One wave per (pair,
+ * permutation) and one per pair for the statistics: u ascending, lane l takes v = u + 1 + l, + 64, ... and adds its terms in
+ * that order; the 64 partial sums meet in the butterfly of xps_silhouette_from_sums_f64.
+ * Words of a pair (XPS_RSA_PAIR_WORDS each): 0 A (DEVICE, float64), 1 lda, 2 na (A is na x na), 3 the offset of ia in idx, 4 B,
+ * 5 ldb, 6 nb, 7 the offset of ib in idx, 8 m, 9 its permutation table, 10 its output row.  tables: int64[2 n_tables] = {offset
+ * in perms, m}; table t is perms[offset .. offset + (R + 1) m) as (R + 1, m) int32 and may be shared by every pair of that m.
+ * idx (int32[n_idx]) and perms (int32[n_perm]) are HOST arrays like the tables.  stats is (n_rows, 4), cross (n_rows, R + 1),
+ * DEVICE; output rows of two pairs must differ.  Refused: null tables, matrices or outputs, negative counts, lda < na, ldb < nb,
+ * m < 2 or m > XPS_RSA_MAX_CONDITIONS, an index list outside idx, an index at or past the matrix size, a table outside perms or
+ * of another m than its pair, a table row that is not a permutation of [0, m) (a repeated or out-of-range entry), a row 0 that
+ * is not the identity, an output row outside [0, n_rows), R < 0, cosine outside 0 / 1, a null or too small workspace. */
+#define XPS_RSA_STD_WORDS 8
+#define XPS_RSA_RDM_WORDS 8
+#define XPS_RSA_PAIR_WORDS 12
+#define XPS_RSA_MAX_CONDITIONS 1024
+size_t xps_row_standardize_grouped_f64_workspace(int n_problems);
+int xps_row_standardize_grouped_f64(const int64_t* problems, int n_problems, void* ws, size_t ws_bytes, void* stream);
+size_t xps_rdm_from_corr_grouped_f64_workspace(int n_problems);
+int xps_rdm_from_corr_grouped_f64(const int64_t* problems, int n_problems, void* ws, size_t ws_bytes, void* stream);
+size_t xps_rdm_compare_perm_f64_workspace(int n_pairs, int n_tables, int64_t n_idx, int64_t n_perm);
+int xps_rdm_compare_perm_f64(const int64_t* pairs, int n_pairs, const int64_t* tables, int n_tables, const int32_t* idx,
+                             int64_t n_idx, const int32_t* perms, int64_t n_perm, int R, int cosine, double* stats, double* cross,
+                             int64_t n_rows, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
