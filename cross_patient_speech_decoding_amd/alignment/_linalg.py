@@ -1356,3 +1356,105 @@ def rdm_compare_perm(pairs, idx, tables, perms, R, cosine=False):
     call('xps_rdm_compare_perm_f64', tab.ctypes.data, n, tables.ctypes.data, len(tables), idx.ctypes.data, len(idx), perms.ctypes.data,
          len(perms), R, int(bool(cosine)), stats.data_ptr(), cross.data_ptr(), n, ws.data_ptr(), nb, stream())
     return stats, cross, (tab, tables, idx, perms, ws)
+
+
+# ------------------------------------------------------------------------------------ TME surrogates (csrc/xps_tme.hip)
+TME_KRON_WORDS, TME_MAX_AXIS = 20, 1024                      # XPS_TME_KRON_WORDS, XPS_TME_MAX_AXIS of include/xps.h
+# the words of a problem (include/xps.h)
+(KP_K0, KP_K1, KP_K2, KP_L0, KP_L1, KP_L2, KP_W1_0, KP_W1_1, KP_W1_2, KP_W2_0, KP_W2_1, KP_W2_2, KP_P01, KP_LD01, KP_P02, KP_LD02,
+ KP_P12, KP_LD12, KP_SCAL) = range(19)
+
+
+def _check_f64_vector(v, n, what):
+    if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == F64 and v.dim() == 1 and v.is_contiguous() and v.shape[0] == n):
+        raise ValueError(f'{what}: a contiguous float64 device vector of {n} elements is needed')
+    return v.data_ptr()
+
+
+def tme_kron_pass(problems):
+    """problems: list of dicts with the float64 device tensors l (three multiplier vectors of k0, k1, k2 elements), w1 and w2
+    (three vectors each: the single-axis marginals of W = 1 / (l0_i + l1_j + l2_k) and of W^2), p01 (k0, k1), p02 (k0, k2), p12
+    (k1, k2) (the pairwise marginals of W^2; matrices with contiguous rows) and scal (2: sum log D, the number of axis-0 slabs with a
+    D <= 0).  ONE xps_tme_kron_pass_f64 call for all problems.  Returns the host table and workspace of the call, which the
+    caller keeps until it has synchronised with the stream."""
+    n = len(problems)
+    if n == 0:
+        return None
+    if n > 65535:
+        raise ValueError(f'tme_kron_pass: {n} problems; at most 65535 go into one call')
+    tab = np.zeros((n, TME_KRON_WORDS), dtype=np.int64)
+    for row, pr in zip(tab, problems):
+        k = [int(v.shape[0]) if isinstance(v, torch.Tensor) and v.dim() == 1 else -1 for v in pr['l']]
+        if len(k) != 3 or not all(1 <= x <= TME_MAX_AXIS for x in k):
+            raise ValueError(f'tme_kron_pass: three multiplier vectors of 1 .. XPS_TME_MAX_AXIS = {TME_MAX_AXIS} elements are needed')
+        row[KP_K0:KP_K0 + 3] = k
+        for r in range(3):
+            row[KP_L0 + r] = _check_f64_vector(pr['l'][r], k[r], 'tme_kron_pass l')
+            row[KP_W1_0 + r] = _check_f64_vector(pr['w1'][r], k[r], 'tme_kron_pass w1')
+            row[KP_W2_0 + r] = _check_f64_vector(pr['w2'][r], k[r], 'tme_kron_pass w2')
+        for key, word, shape in (('p01', KP_P01, (k[0], k[1])), ('p02', KP_P02, (k[0], k[2])), ('p12', KP_P12, (k[1], k[2]))):
+            _check_f64_matrix(pr[key], 'tme_kron_pass ' + key)
+            if tuple(pr[key].shape) != shape:
+                raise ValueError(f'tme_kron_pass: {key} must have shape {shape}')
+            row[word], row[word + 1] = pr[key].data_ptr(), max(pr[key].stride(0), shape[1])
+        row[KP_SCAL] = _check_f64_vector(pr['scal'], 2, 'tme_kron_pass scal')
+    tab = np.ascontiguousarray(tab.reshape(-1))
+    nb = int(lib().xps_tme_kron_pass_f64_workspace(n))
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=device())
+    call('xps_tme_kron_pass_f64', tab.ctypes.data, n, ws.data_ptr(), nb, stream())
+    return tab, ws
+
+
+def tme_core_scale(z, ls, out=None):
+    """core = z * sqrt(W), W_ijk = 1 / (l0_i + l1_j + l2_k), for z (S, k0, k1, k2): a float64 device tensor whose rows (the last
+    axis) are contiguous and evenly spaced (a contiguous tensor, or one padded along its last axis).  out: the same kind of
+    tensor (default: a new contiguous one; may be z).  ONE launch."""
+    if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == F64 and z.dim() == 4):
+        raise ValueError('tme_core_scale: z must be an (S, k0, k1, k2) float64 device tensor')
+    S, k0, k1, k2 = (int(v) for v in z.shape)
+    if not all(1 <= x <= TME_MAX_AXIS for x in (k0, k1, k2)):
+        raise ValueError(f'tme_core_scale: every box size must lie in 1 .. XPS_TME_MAX_AXIS = {TME_MAX_AXIS}')
+    out = torch.empty((S, k0, k1, k2), dtype=F64, device=z.device) if out is None else out
+    lds = []
+    for t, what in ((z, 'z'), (out, 'out')):
+        ld = max(int(t.stride(2)), k2) if isinstance(t, torch.Tensor) and t.dim() == 4 else 0
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == F64 and tuple(t.shape) == (S, k0, k1, k2)
+                and (k2 == 1 or t.stride(3) == 1) and (k1 == 1 or t.stride(2) == ld) and (k0 == 1 or t.stride(1) == k1 * ld)
+                and (S <= 1 or t.stride(0) == k0 * k1 * ld)):
+            raise ValueError(f'tme_core_scale: {what} must be a float64 device tensor of shape {(S, k0, k1, k2)} with evenly spaced rows')
+        lds.append(ld)
+    ptrs = [_check_f64_vector(v, k, 'tme_core_scale l') for v, k in zip(ls, (k0, k1, k2))]
+    call('xps_tme_core_scale_f64', z.data_ptr(), lds[0], ptrs[0], ptrs[1], ptrs[2], k0, k1, k2, S, out.data_ptr(), lds[1], stream())
+    return out
+
+
+def tme_mode_product(A, B, C, b_kcontig=False, add=None):
+    """C[b] = A[b] @ op(B[b]) + add for every member b of a batch in ONE xps_tme_mode_product_f64 launch.  A (M, K) or (batch, M, K),
+    B (K, N) or (batch, K, N) -- with b_kcontig (N, K) or (batch, N, K), multiplied as its transpose --, add (M, N) or None, C
+    (batch, M, N) float64 or float32: device tensors with contiguous rows; a 2-D operand is shared by the batch.  The batch axis
+    of an operand may have any non-negative stride."""
+    def mat(t, what, dtypes=(F64,)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and t.dim() in (2, 3) and t.shape[-1] >= 1
+                and (t.shape[-1] == 1 or t.stride(-1) == 1) and t.stride(-2) >= 0):
+            raise ValueError(f'tme_mode_product: {what} must be a 2-D or 3-D device tensor with contiguous rows')
+        return max(int(t.stride(-2)), int(t.shape[-1])), (int(t.stride(0)) if t.dim() == 3 else 0)
+    lda, sa = mat(A, 'A')
+    ldb, sb = mat(B, 'B')
+    if C.dim() != 3:
+        raise ValueError('tme_mode_product: C must be (batch, M, N)')
+    ldc, sc = mat(C, 'C', (F64, torch.float32))
+    batch, M, N = (int(v) for v in C.shape)
+    K = int(A.shape[-1])
+    if (tuple(A.shape[-2:]) != (M, K) or tuple(B.shape[-2:]) != ((N, K) if b_kcontig else (K, N))
+            or any(t.dim() == 3 and t.shape[0] != batch for t in (A, B)) or sa < 0 or sb < 0 or K < 1):
+        raise ValueError('tme_mode_product: the shapes of A, B and C do not fit together')
+    if batch > 1 and sc < (M - 1) * ldc + N:
+        raise ValueError('tme_mode_product: the outputs of two batch members overlap')
+    ldadd = 0
+    if add is not None:
+        ldadd, _ = mat(add, 'add')
+        if add.dim() != 2 or tuple(add.shape) != (M, N):
+            raise ValueError('tme_mode_product: add must be (M, N)')
+    call('xps_tme_mode_product_f64', A.data_ptr(), lda, sa, B.data_ptr(), ldb, sb, int(bool(b_kcontig)), ptr(add), ldadd, C.data_ptr(),
+         _is32(C), ldc, sc, M, N, K, batch, stream())
+    return C

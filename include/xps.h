@@ -1287,6 +1287,54 @@ int xps_rdm_compare_perm_f64(const int64_t* pairs, int n_pairs, const int64_t* t
                              int64_t n_idx, const int32_t* perms, int64_t n_perm, int R, int cosine, double* stats, double* cross,
                              int64_t n_rows, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Tensor maximum entropy surrogates (csrc/xps_tme.hip; surrogates/tme.py;        */
+/* DESIGN.md 4.24): random tensors with a data tensor's marginal covariances.     */
+/* ------------------------------------------------------------------------- */
+/* Float64, no atomics; every sum is taken in an order that is a function of the problem alone, so a problem's bits do not depend
+ * on the grid, the stream, the other problems of a call or the chunking of a batch.  Nothing allocates or synchronises; every
+ * refusal is XPS_E_INVALID before any launch.
+ *
+ * xps_tme_kron_pass_f64 takes xps_gram_grouped_f64's convention: a HOST table of int64 words, checked by the call and copied into
+ * ws (DEVICE, ..._workspace(n_problems) bytes) on the stream.  For every problem, with W_ijk = 1 / D_ijk and
+ * D_ijk = (l0[i] + l1[j]) + l2[k] over the k0 x k1 x k2 box (never stored):
+ *     w1_r[a] = sum of W over the two other axes,   w2_r[a] = the same sum of W^2            (r = 0, 1, 2)
+ *     p01[i][j] = sum_k W^2,   p02[i][k] = sum_j W^2,   p12[j][k] = sum_i W^2
+ *     scal[0] = sum log D,   scal[1] = the number of axis-0 slabs i that hold a D <= 0 (or NaN): 0 when every D is positive.
+ * Workgroup (a, problem) owns index a of ONE axis A and walks the plane of the other two, B = A + 1 and C = A + 2 (mod 3): wave w
+ * takes b = w, w + 4, ..., lane l adds its terms c = l, l + 64, ... in that order (D = (l_A[a] + l_B[b]) + l_C[c]), the 64 partial
+ * sums of a row (a, b) meet in the butterfly of xps_silhouette_from_sums_f64 -- that is the pairwise marginal over (A, B): p01 for
+ * A = 0, p12 for A = 1, the TRANSPOSE of p02 for A = 2 --, a wave adds its rows in ascending b and the four waves meet as
+ * (w0 + w1) + (w2 + w3).  The three roles are one code path: a problem whose axes are rotated gives the rotated outputs bit for bit.
+ * sum log D is taken by the role-0 workgroups in the same order and added over i by a second launch (thread t takes i = t, t + 256,
+ * ... ascending; a fixed tree).  Each role evaluates 1 / D itself: three divisions per box element instead of a k0 x k1 x k2 array
+ * and a cross-workgroup reduction.  Outputs of a problem with a D <= 0 hold infinities or NaN; other problems are not touched.
+ * Words of a problem (XPS_TME_KRON_WORDS each): 0-2 k0 k1 k2 (1 .. XPS_TME_MAX_AXIS), 3-5 l0 l1 l2 (DEVICE), 6-8 w1_0 w1_1 w1_2,
+ * 9-11 w2_0 w2_1 w2_2, 12 p01, 13 ld01 (>= k1), 14 p02, 15 ld02 (>= k2), 16 p12, 17 ld12 (>= k2), 18 scal (2 doubles).  At most
+ * 65535 problems.  Refused: a null table, vector, marginal or scalar pair, a negative count, a box size outside
+ * 1 .. XPS_TME_MAX_AXIS, a leading dimension below its width, a null or too small workspace.
+ *
+ * xps_tme_core_scale_f64: core[row][k] = z[row][k] * sqrt(1 / D_ijk) for the n_sur k0 k1 rows row = (s k0 + i) k1 + j of n_sur
+ * surrogates, z with row stride ldz >= k2 and core with ldc >= k2; core may be z when ldc == ldz.  Refused: null pointers,
+ * negative counts, a box size outside 1 .. XPS_TME_MAX_AXIS, ldz < k2, ldc < k2, more than 2^20 surrogates.
+ *
+ * xps_tme_mode_product_f64: C[b] = A[b] op(B[b]) + add for b = 0 .. batch - 1 on the f64 MFMA tile of xps_f64_tile.h, the
+ * contraction ascending.  A[b] = A + b sa is M x K (element (m, k) at m lda + k); B[b] = B + b sb is K x N (element (k, n) at
+ * k ldb + n), or with b_kcontig = 1 stored as N x K (element at n ldb + k); a stride of 0 shares the operand.  add (or null) is
+ * M x N with ldadd, shared by the batch; C[b] = C + b sc elements with ldc, float32 when c_is_f32.  The mode products of S
+ * surrogates are three calls: the middle one is batch = S k0 products on the slices where they lie.  Refused: null
+ * matrices, negative sizes or strides, K < 1, lda < K, ldb below B's width, ldc < N, ldadd < N, batch outputs that overlap
+ * (sc < (M - 1) ldc + N), more than 2^31 - 1 tiles. */
+#define XPS_TME_KRON_WORDS 20
+#define XPS_TME_MAX_AXIS 1024
+size_t xps_tme_kron_pass_f64_workspace(int n_problems);
+int xps_tme_kron_pass_f64(const int64_t* problems, int n_problems, void* ws, size_t ws_bytes, void* stream);
+int xps_tme_core_scale_f64(const double* z, int64_t ldz, const double* l0, const double* l1, const double* l2, int k0, int k1, int k2,
+                           int64_t n_sur, double* core, int64_t ldc, void* stream);
+int xps_tme_mode_product_f64(const double* A, int64_t lda, int64_t sa, const double* B, int64_t ldb, int64_t sb, int b_kcontig,
+                             const double* add, int64_t ldadd, void* C, int c_is_f32, int64_t ldc, int64_t sc, int64_t M, int N, int K,
+                             int64_t batch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
